@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: megapixels/s of the full RAW ISP on synthetic 12 MP RGGB frames.
 
-  python bench.py --gpus N --steps K --warmup W [--workload isp|rcd|ppg_wiener50] [--storage f16|f32]
+  python bench.py --gpus N --steps K --warmup W [--workload isp|rcd|ppg_wiener50] [--storage f16|f32] [--full] [--dump-outputs DIR]
 
 One step = one pass of the hot path over one batch of device-resident synthetic frames per GPU:
   isp (BASELINE.json configs[2], the configuration the metric is quoted on):
@@ -26,13 +26,18 @@ itself (the parent never touches the GPU, it only relays rank 0's line); under
 used as they are.  The number of ranks that ran must equal --gpus or the run fails: a line with
 `n_gpus` different from `--gpus` cannot be printed.
 
-Prints ONE JSON line on rank 0 (contract in the task description): metric/value/unit...,
+Prints ONE JSON line on rank 0 (contract in the task description): metric/value/unit/ms_per_step...  A plain run only sets
+up, warms up, times --steps steps and prints that line.  With --full it also reports
 "roofline" for the dominant kernel = its HBM fraction: the algorithmic bytes of the stage it implements
 divided by its average launch time (measured live with HIP events on the launch stream by the library's tdk_profile_*
 timer) against 8 TB/s; the vector-ALU issue floors (which are what actually bound these kernels) are reported beside it
 under "valu" / "composite", never as `frac`; "cpu_baseline" (the strict-fp32 CPU oracle, i.e. a port -- the reference has
 no CPU path -- timed on a bounded sample) and "parity_check": the uint8 output of GPU frame 0 in the last timed step
 against the oracle's output for the same input.  Exit code 3 if that check fails.
+
+--dump-outputs DIR writes what rank 0's last timed step returned (one output image per frame) as float32 .npy files, a fixed
+seeded sample of pixels when the whole batch would not fit DUMP_MAX_BYTES (dump_outputs()).  The inputs depend only on the
+arguments, so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -66,6 +71,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 GB/
 
 W12, H12 = 4096, 3072
 W50, H50 = 8192, 6144
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: the sampled values of all frames plus their pixel index stay below this
 
 
 def parse_args(argv=None):
@@ -82,9 +88,14 @@ def parse_args(argv=None):
     ap.add_argument('--graph', action='store_true', help='replay each step as one captured HIP graph (measurement option; no live per-kernel timing)')
     ap.add_argument('--width', type=int, default=None)
     ap.add_argument('--height', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU oracle run (and with it the parity check)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: the per-kernel table and the roofline '
+                         '(untimed profiling passes, the dominant kernel timed live), the CPU oracle baseline and the parity check')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write rank 0's outputs of the last timed step to DIR/<name>.npy (float32, a fixed seeded pixel sample)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU oracle run (and with it the parity check)')
     ap.add_argument('--pin-cpus', action='store_true', help='self-launched ranks: give each rank its own slice of the host cores (os.sched_setaffinity)')
-    ap.add_argument('--no-kernel-timer', action='store_true', help='leave the per-kernel event timer off in the timed region')
+    ap.add_argument('--no-kernel-timer', action='store_true', help='--full: leave the per-kernel event timer off in the timed region')
     ap.add_argument('--stub-cpu', action='store_true',
                     help='REHEARSAL ONLY (tests/test_bench_launch.py): run the rank/launch/timing protocol on the CPU with a stand-in '
                          'stage instead of the HIP pipeline; the line is labelled "stub" and is not a measurement')
@@ -466,6 +477,26 @@ def parity_check(workload, gpu_out, oracle_out):
     return {'ok': None, 'skipped': 'no full-frame oracle sample for this workload'}
 
 
+def dump_outputs(outs, out_dir, seed: int = 1234) -> None:
+    """--dump-outputs: the (H, W, C) output images of one step as DIR/frame<i>.npy, float32 of shape (P, C) -- the values at P
+    pixel positions drawn once from `seed` (the same positions for every frame and every run; all H*W when the batch fits
+    DUMP_MAX_BYTES) -- and DIR/pixel_index.npy, those flat positions (row * W + col) as float64."""
+    import numpy as np
+    import torch
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    h, w = outs[0].shape[:2]
+    c = outs[0].numel() // (h * w)
+    n = h * w
+    p = min(n, DUMP_MAX_BYTES // (4 * c * len(outs) + 8))
+    idx = np.arange(n) if p == n else np.sort(np.random.default_rng(seed).choice(n, p, replace=False))
+    np.save(out_dir / 'pixel_index.npy', idx.astype(np.float64))
+    idx_t = torch.from_numpy(idx).to(outs[0].device)
+    for i, o in enumerate(outs):
+        np.save(out_dir / f'frame{i}.npy', o.reshape(n, c).index_select(0, idx_t).float().cpu().numpy())
+
+
 def _git_head() -> str | None:
     """Short hash of the sources being measured: from git, or (GPU-box snapshots carry no .git) from the
     .git_head file a post-commit hook keeps next to the sources."""
@@ -490,15 +521,17 @@ def run_stub(args, ranks: Ranks, pinned=None):
     inputs = [synthetic_bayer(h, w, seed=1234 + ranks.rank * frames + i, device='cpu') for i in range(frames)]
 
     def step():
-        return [torch.nn.functional.avg_pool2d(b.permute(2, 0, 1)[None], 3, 1, 1) for b in inputs]
+        return [torch.nn.functional.avg_pool2d(b.permute(2, 0, 1)[None], 3, 1, 1)[0].permute(1, 2, 0) for b in inputs]
 
     for _ in range(args.warmup):
         step()
     ranks.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        outs = step()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and ranks.rank == 0:
+        dump_outputs(outs, args.dump_outputs)
     ranks.barrier()
     per_rank = ranks.gather(elapsed)
     ncpus = ranks.gather(float(len(os.sched_getaffinity(0))))
@@ -521,6 +554,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit('bench.py: --gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be >= 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # no launcher: start the N ranks ourselves, BEFORE anything in this process touches the GPU
         return launch_ranks(args, argv)
@@ -558,7 +593,8 @@ def main(argv=None):
     nstreams = max(1, min(args.streams, frames))
     from torch_darktable.sharding import FrameStreams
 
-    dtype, process = build_pipeline(td, dev, w, h, storage, args.workload, args.chain)
+    dtype = torch.float16 if storage == 'f16' else torch.float32
+    process = build_pipeline(td, dev, w, h, storage, args.workload, args.chain)[1] if args.full else None  # step_serial's chain (--full)
     runner = FrameStreams(dev, lambda: build_pipeline(td, dev, w, h, storage, args.workload, args.chain)[1], streams=nstreams)
 
     # device-resident synthetic inputs, per-frame seeds 1234 + i (distinct per rank)
@@ -579,7 +615,7 @@ def main(argv=None):
     def step():  # the timed region synchronises the device after its K steps, so the streams are not joined per step
         last[0] = runner.issue(inputs)
 
-    use_timer = not args.no_kernel_timer
+    use_timer = args.full and not args.no_kernel_timer
     if args.graph:
         # one step = one replay of the batch captured as a HIP graph (FrameStreams.capture): the host launches one graph instead of
         # ~57 kernels.  Events cannot bracket a kernel inside a graph, so this mode carries no live roofline kernel time.
@@ -636,6 +672,8 @@ def main(argv=None):
         return 0
     if len(per_rank) != args.gpus:
         raise SystemExit(f'bench.py: {len(per_rank)} ranks ran but --gpus is {args.gpus}')
+    if args.dump_outputs:
+        dump_outputs(last[0], args.dump_outputs)
 
     mp_per_frame = w * h / 1e6
     total_frames = frames * args.steps * world
@@ -766,7 +804,7 @@ def main(argv=None):
         'git': _git_head(),
     }
     rc = 0
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             frame0 = inputs[0].float().cpu().numpy()  # what GPU frame 0 read (binary16 values for fp16 storage), after the timed region
             out['cpu_baseline'], oracle_out = cpu_baseline(args.workload, os.cpu_count() or 1, frame0)

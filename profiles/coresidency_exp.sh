@@ -5,7 +5,7 @@
 LIB=${LIB:-variants/exp.so}
 for cfg in "$@"; do
   IFS='|' read -r label envs bargs <<< "$cfg"
-  line=$(env TDK_LIB_PATH=$LIB $envs python bench.py --no-cpu-baseline --steps ${STEPS:-200} $bargs 2>/dev/null | tail -1)
+  line=$(env TDK_LIB_PATH=$LIB $envs python bench.py --full --no-cpu-baseline --steps ${STEPS:-200} $bargs 2>/dev/null | tail -1)
   python3 - "$label" "$envs" "$bargs" "$line" <<'PY'
 import json, sys
 label, envs, bargs, line = sys.argv[1:5]

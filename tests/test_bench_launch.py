@@ -11,6 +11,7 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
+VISIBLE_DEVICES = ('ROCR_VISIBLE_DEVICES', 'HIP_VISIBLE_DEVICES', 'CUDA_VISIBLE_DEVICES')
 
 
 def _run(extra, env_extra=None, drop=('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')):
@@ -82,11 +83,12 @@ def test_gpus8_rehearsal_eight_ranks():
     assert r.stdout.count('{') >= 1 and len(_json_lines(r.stdout)) == 1  # no rank but 0 prints a line
 
 
-def test_gpus8_rehearsal_with_pinned_ranks():
+def test_gpus8_rehearsal_with_pinned_ranks(tmp_path):
     """--pin-cpus: the parent cuts the host cores it may use into one slice per rank and every child pins itself to its slice
     before it starts a thread; the line reports the cores each rank ended up with (8 ranks on this container's 8 cores: one
-    each) -- rank r's launch thread cannot migrate onto another rank's core."""
-    r = _run(['--gpus', '8', '--pin-cpus'], env_extra={'OMP_NUM_THREADS': '1'})
+    each) -- rank r's launch thread cannot migrate onto another rank's core.  The sysfs tree is an empty one (no GPU NUMA
+    nodes: the plain index split), whatever GPUs the host has; the NUMA-aware split is pinned below on fake trees."""
+    r = _run(['--gpus', '8', '--pin-cpus'], env_extra={'OMP_NUM_THREADS': '1', 'TDK_BENCH_SYSFS': str(tmp_path)})
     assert r.returncode == 0, r.stderr
     (out,) = _json_lines(r.stdout)
     ncores = len(os.sched_getaffinity(0))
@@ -115,9 +117,11 @@ def _fake_sysfs(root, gpu_nodes, node_cpus):
         (nd / 'cpulist').write_text(cpulist + '\n')
 
 
-def test_numa_cpu_slices_follow_the_gpus_numa_nodes(tmp_path):
+def test_numa_cpu_slices_follow_the_gpus_numa_nodes(tmp_path, monkeypatch):
     """Each rank's cores come from ITS GPU's NUMA node (KFD topology -> PCI address -> numa_node -> cpulist, sysfs only), shared
     evenly among the ranks on that node; unknown nodes fall back to the plain index split; *_VISIBLE_DEVICES re-maps."""
+    for var in VISIBLE_DEVICES:  # the host's own device selection would re-map the fake tree
+        monkeypatch.delenv(var, raising=False)
     sys.path.insert(0, str(ROOT))
     import bench
 
@@ -141,11 +145,8 @@ def test_numa_cpu_slices_follow_the_gpus_numa_nodes(tmp_path):
     assert bench.numa_cpu_slices(8, str(other), allowed) == [list(range(16 * r, 16 * r + 16)) for r in range(8)]
     assert bench.numa_cpu_slices(4, str(tmp_path / 'missing'), list(range(8))) == [[0, 1], [2, 3], [4, 5], [6, 7]]
     # HIP_VISIBLE_DEVICES re-orders the devices a rank sees
-    os.environ['HIP_VISIBLE_DEVICES'] = '4,5,0,1'
-    try:
-        assert bench.gpu_numa_nodes(str(tmp_path)) == [0, 0, 1, 1]
-    finally:
-        del os.environ['HIP_VISIBLE_DEVICES']
+    monkeypatch.setenv('HIP_VISIBLE_DEVICES', '4,5,0,1')
+    assert bench.gpu_numa_nodes(str(tmp_path)) == [0, 0, 1, 1]
 
 
 def test_ranks_under_an_external_launcher_pin_themselves_numa_aware(tmp_path):
@@ -165,7 +166,7 @@ def test_ranks_under_an_external_launcher_pin_themselves_numa_aware(tmp_path):
         port = sk.getsockname()[1]
     procs = []
     for rank in range(2):
-        env = dict(os.environ, WORLD_SIZE='2', LOCAL_WORLD_SIZE='2', RANK=str(rank), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port),
+        env = dict({k: v for k, v in os.environ.items() if k not in VISIBLE_DEVICES}, WORLD_SIZE='2', LOCAL_WORLD_SIZE='2', RANK=str(rank), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port),
                    TDK_BENCH_SYSFS=str(tmp_path), OMP_NUM_THREADS='1')
         procs.append(subprocess.Popen([sys.executable, str(ROOT / 'bench.py'), '--stub-cpu', '--gpus', '2', '--steps', '2', '--warmup', '1'],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env))
@@ -173,3 +174,46 @@ def test_ranks_under_an_external_launcher_pin_themselves_numa_aware(tmp_path):
     assert [p.returncode for p in procs] == [0, 0], outs
     (line,) = _json_lines(outs[0][0])
     assert line['pinned'] is True and line['cpus_per_rank'] == [half, half]
+
+
+def test_dump_outputs_same_arguments_same_files(tmp_path):
+    """--dump-outputs DIR: the outputs of the last timed step as float32 .npy files, identical from run to run with the same
+    arguments (the stub's 64x64 frames fit whole: every pixel, in order)."""
+    import numpy as np
+
+    for d in ('a', 'b'):
+        r = _run(['--gpus', '1', '--dump-outputs', str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == ['frame0.npy', 'frame1.npy', 'pixel_index.npy']
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.load(tmp_path / 'a' / 'frame0.npy').shape == (64 * 64, 1)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'pixel_index.npy'), np.arange(64 * 64))
+
+
+def test_dump_outputs_samples_a_batch_that_does_not_fit(tmp_path, monkeypatch):
+    """A batch larger than DUMP_MAX_BYTES is dumped as the values at a fixed seeded set of pixels, the same for every frame;
+    the default budget keeps the 12 MP isp batch (8 frames x 3 channels) under 64 MB."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    n_isp = bench.W12 * bench.H12
+    p_isp = min(n_isp, bench.DUMP_MAX_BYTES // (4 * 3 * 8 + 8))
+    assert p_isp < n_isp and p_isp * (4 * 3 * 8 + 8) + 9 * 128 <= 64e6
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 1 << 16)
+    g = torch.Generator().manual_seed(0)
+    outs = [torch.randint(0, 256, (48, 64, 3), generator=g, dtype=torch.uint8) for _ in range(3)]
+    bench.dump_outputs(outs, tmp_path / 'a')
+    bench.dump_outputs(outs, tmp_path / 'b')
+    idx = np.load(tmp_path / 'a' / 'pixel_index.npy')
+    assert idx.dtype == np.float64 and 0 < len(idx) < 48 * 64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / 'b' / 'pixel_index.npy'))
+    for i, o in enumerate(outs):
+        got = np.load(tmp_path / 'a' / f'frame{i}.npy')
+        assert got.dtype == np.float32 and np.array_equal(got, o.reshape(-1, 3).numpy()[idx.astype(np.int64)].astype(np.float32))
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').iterdir()) <= (1 << 16) + 4 * 128
