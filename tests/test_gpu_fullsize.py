@@ -40,6 +40,21 @@ def window(t, y0, x0, size, margin):
 WINDOWS = [(1024, 2048), (2000, 304), (64, 3504)]  # (y0, x0): multiples of 8 (CFA phase, Wiener tile grid, bilateral cells)
 
 
+def edge_windows(w, h, n=256):
+    """(y0, y1, x0, x1): a window on the bottom edge, one on the right edge and the bottom-right corner.  They start on the last
+    multiple of 8 that leaves at least n pixels and run to the frame's edge."""
+    yb, xr = 8 * ((h - n) // 8), 8 * ((w - n) // 8)
+    return [(yb, h, 1024, 1024 + n), (1024, 1024 + n, xr, w), (yb, h, xr, w)]
+
+
+def edge_crop(t, win, margin):
+    """numpy copy of the window plus `margin` on its inner sides (none past the frame's edge) and the window's offset in it."""
+    y0, y1, x0, x1 = win
+    h, w = t.shape[:2]
+    cy0, cx0 = max(y0 - margin, 0), max(x0 - margin, 0)
+    return npy(t[cy0:min(y1 + margin, h), cx0:min(x1 + margin, w)]).copy(), (slice(y0 - cy0, y1 - cy0), slice(x0 - cx0, x1 - cx0))
+
+
 def test_rcd_12mp_crop_consistency_and_native(td, oracle, dev, frame12):
     out = td.RCD(dev, (W12, H12), td.BayerPattern.RGGB).process(frame12)
     assert out.shape == (H12, W12, 3)
@@ -153,6 +168,24 @@ def test_wiener_12mp(td, oracle, dev, frame12):
         assert np.abs(got - ref).max() < 5e-5, f'window {(y0, x0)}: {np.abs(got - ref).max()}'
 
 
+@pytest.mark.parametrize('shape', [(W12, H12), (4096 + 2, 3072 - 31)])
+def test_wiener_12mp_right_and_bottom_edges(td, oracle, dev, shape):
+    """The y-streaming kernel's last, partial segment of each strip (its length comes from pick_segment_rows, csrc/wiener.hip, and
+    only big frames have one) and the frame's last tile row / column.  4098 x 3041: a partial last strip and the scalar load path
+    (W % 4 != 0)."""
+    from torch_darktable.synthetic import synthetic_bayer
+
+    w, h = shape
+    bayer = synthetic_bayer(h, w, seed=1234, device=dev)
+    ll = td.compute_log_luminance(td.RCD(dev, (w, h), td.BayerPattern.RGGB).process(bayer), 1e-4)
+    den = td.Wiener(dev, (w, h), overlap_factor=4, tile_size=32).process(ll.unsqueeze(2), 0.075).squeeze(2)
+    for win in edge_windows(w, h):
+        crop, (ys, xs) = edge_crop(ll, win, 32)
+        ref = oracle.wiener(crop[:, :, None], 0.075, 32, 4)[ys, xs, 0]
+        got = npy(den[win[0]:win[1], win[2]:win[3]])
+        assert np.abs(got - ref).max() < 5e-5, f'{shape} window {win}: {np.abs(got - ref).max()}'
+
+
 def test_bilateral_12mp(td, oracle, dev, frame12):
     rgb = td.RCD(dev, (W12, H12), td.BayerPattern.RGGB).process(frame12)
     lum = td.compute_luminance(rgb)
@@ -165,6 +198,11 @@ def test_bilateral_12mp(td, oracle, dev, frame12):
         ref = oracle.bilateral(window(lum, y0, x0, n, m), 2.0, 0.2, 0.4)[m:-m, m:-m]
         got = npy(out[y0:y0 + n, x0:x0 + n])
         assert np.array_equal(got, ref), f'window {(y0, x0)}: {np.abs(got - ref).max()}'
+    win = edge_windows(W12, H12)[-1]  # the bottom-right corner: the grid's last cells on both axes
+    crop, (ys, xs) = edge_crop(lum, win, m)
+    got = npy(out[win[0]:win[1], win[2]:win[3]])
+    ref = oracle.bilateral(crop, 2.0, 0.2, 0.4)[ys, xs]
+    assert np.array_equal(got, ref), f'window {win}: {np.abs(got - ref).max()}'
 
 
 def test_full_pipeline_12mp_fp16_vs_fp32_oracle(td, oracle, dev, frame12):
@@ -220,5 +258,9 @@ def test_config5_50mp_ppg_wiener_fp16(td, oracle, dev):
     m = 32
     refw = oracle.wiener(window(rgb, y0, x0, n, m), 0.05, 32, 4)[m:-m, m:-m]
     assert np.abs(npy(den[y0:y0 + n, x0:x0 + n]) - refw).max() < 2e-3  # fp16 output rounding
+    win = edge_windows(W50, H50)[-1]  # the bottom-right corner: last strip, last segment, last tile row and column
+    crop, (ys, xs) = edge_crop(rgb, win, m)
+    refw = oracle.wiener(crop, 0.05, 32, 4)[ys, xs]
+    assert np.abs(npy(den[win[0]:win[1], win[2]:win[3]]) - refw).max() < 2e-3
     ident = ws.process(rgb, 0.0)
     assert (ident.float() - rgb.float()).abs().max().item() < 2e-3

@@ -153,3 +153,62 @@ def test_lab_chain_argument_checks(td, dev):
         wiener.process_log_luminance_lab(x[:32], 0.05)
     with pytest.raises(RuntimeError):
         wiener.process_log_luminance_lab(x, 0.05, chroma_out=torch.empty(64, 64, 2, device=dev, dtype=torch.float16))
+
+
+def _tile_kernel_cases():
+    """The geometries and sigmas of test_gpu_parity.py::test_bilateral_tile_kernel_geometry_sweep (the same seeded draw)."""
+    rng = np.random.default_rng(99)
+    cases = [(64, 32, 2.0, 0.2), (65, 33, 2.0, 0.2), (128, 64, 1.5, 0.25), (130, 70, 4.0, 0.1), (67, 200, 3.3, 0.05), (400, 37, 1.0, 0.25), (36, 40, 2.7, 0.02)]
+    cases += [(int(rng.integers(40, 500)), int(rng.integers(40, 300)), float(rng.uniform(1.0, 4.0)), float(rng.choice([0.02, 0.07, 0.1, 0.2, 0.25]))) for _ in range(12)]
+    return cases
+
+
+def test_lab_chain_tile_kernel_geometry_sweep(td, oracle, dev, scene):
+    """process_lab's tile kernel (bt_fast: contraction on, so not bit-exact) over frame sizes that end in partial tiles on either
+    axis, widths that are / are not multiples of 4 (VEC = 4 / 1), sigma_s from 1 to 4 and short and long z columns: within 2 * TOL of
+    the oracle chain and of the general four-kernel Lab path; the float16 result is the float32 result rounded once."""
+    from torch_darktable import torch_darktable_extension as ext
+
+    cases = _tile_kernel_cases()
+    assert any(w % 4 for w, _, _, _ in cases) and any(w % 4 == 0 for w, _, _, _ in cases)
+    for k, (w, h, ss, sr) in enumerate(cases):
+        rgb = scene(h, w, 200 + k)
+        x = torch.from_numpy(rgb).to(dev)
+        bil = td.Bilateral(dev, (w, h), sigma_s=ss, sigma_r=sr)
+        lum, ab = td.Wiener(dev, (w, h), overlap_factor=4, tile_size=32).process_log_luminance_lab(x, 0.075)
+        out = bil.process_lab(lum, ab, 0.4)
+        out16 = bil.process_lab(lum, ab, 0.4, out_dtype=torch.float16)
+        with ext.verification_paths(bilateral_general=True):  # the general four-kernel path, same parameters
+            general = bil.process_lab(lum, ab, 0.4)
+        ref = oracle_chain(oracle, rgb, ss, sr)[2]
+        what = f'{w}x{h} sigma ({ss:.3f}, {sr})'
+        d = np.abs(npy(out) - ref).max()
+        assert d <= 2 * TOL, (what, 'oracle', d)
+        d = (out - general).abs().max().item()
+        assert d <= 2 * TOL, (what, 'general path', d)
+        assert torch.equal(out16, out.half()), (what, (out16 != out.half()).sum().item())
+
+
+def test_lab_chain_tile_kernel_special_values(td, dev, scene):
+    """Zeros, denormals, huge, negative, infinite and NaN lightness samples: the tile kernel puts NaN / inf where the general path
+    does and agrees with it elsewhere within 2 * TOL."""
+    from torch_darktable import torch_darktable_extension as ext
+
+    w, h = 256, 96
+    rng = np.random.default_rng(98)
+    x = torch.from_numpy(scene(h, w, 64)).to(dev)
+    lum, ab = td.Wiener(dev, (w, h), overlap_factor=4, tile_size=32).process_log_luminance_lab(x, 0.075)
+    special = np.array([0.0, -0.0, 1e-45, 1e-39, 2.0 ** -41, 2.0 ** -40, 2.0 ** 40, 2.0 ** 41, 1e30, -0.3, -1e30, np.inf, -np.inf, np.nan], np.float32)
+    ys, xs = rng.integers(0, h, 200), rng.integers(0, w, 200)
+    plane = npy(lum)
+    plane[ys, xs] = special[rng.integers(0, len(special), 200)]
+    lum = torch.from_numpy(plane).to(dev)
+    bil = td.Bilateral(dev, (w, h), sigma_s=2.0, sigma_r=0.2)
+    a = bil.process_lab(lum, ab, 0.4)
+    with ext.verification_paths(bilateral_general=True):  # the general four-kernel path, same parameters
+        b = bil.process_lab(lum, ab, 0.4)
+    assert torch.equal(torch.isnan(a), torch.isnan(b)), (torch.isnan(a) != torch.isnan(b)).sum().item()
+    assert torch.equal(torch.isinf(a), torch.isinf(b)) and torch.equal(a[torch.isinf(a)], b[torch.isinf(b)])
+    fin = torch.isfinite(a)
+    d = (a[fin] - b[fin]).abs().max().item()
+    assert d <= 2 * TOL, d

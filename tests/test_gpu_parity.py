@@ -763,3 +763,29 @@ def test_raw_frame_stream_prefetch(td, dev, tmp_path):
         list(RawFrameStream([paths[0], b'short'], dev, nb))
     with pytest.raises(ValueError):
         RawFrameStream(paths, torch.device('cpu'), nb)
+
+
+@pytest.mark.parametrize('shape', [(6000, 256), (6002, 256), (8192, 256), (256, 6146)])
+def test_bilateral_grid_clamp_whole_frame(td, oracle, dev, scene, shape):
+    """sigma_s = 2 on frames wider / taller than 6000 px: the grid clamps at 3000 cells a side but the samples still divide by the
+    raw sigma_s (oracle/src/bilateral.c), so every pixel past 6000 collapses onto the last cell.  plan_tiles sends these frames to
+    the four-kernel path: `process` bit for bit, `process_lab` within 2 * TOL of the oracle chain, on the whole frame.  The collapsed
+    cells hold thousands of samples each, so they amplify the chain's tolerated lightness differences (measured 3.6e-7 -> 4.4e-4
+    in the filtered lightness past x = 6000 at 8192 px, 1.8e-6 before it): the oracle's bilateral runs on the GPU's lightness plane,
+    which is itself checked against the oracle's within TOL."""
+    from test_gpu_lab_chain import TOL
+
+    w, h = shape
+    rgb = scene(h, w, 72)
+    ws = td.Bilateral(dev, (w, h), sigma_s=2.0, sigma_r=0.2)
+    assert ws._bilateral.grid_size() == oracle.bilateral_grid_size(w, h, 2.0, 0.2) and max(ws._bilateral.grid_size()[:2]) == 3001
+    lum = oracle.compute_luminance(rgb)
+    got = npy(ws.process(gpu(lum, dev), 0.4))
+    assert np.array_equal(got, oracle.bilateral(lum, 2.0, 0.2, 0.4)), np.abs(got - oracle.bilateral(lum, 2.0, 0.2, 0.4)).max()
+    lab_l, lab_ab = td.Wiener(dev, (w, h), overlap_factor=4, tile_size=32).process_log_luminance_lab(gpu(rgb, dev), 0.075)
+    out = ws.process_lab(lab_l, lab_ab, 0.4)
+    ll = oracle.compute_luminance(rgb, True, 1e-4)
+    den = oracle.modify_luminance(rgb, oracle.wiener(ll[:, :, None], 0.075, 32, 4)[:, :, 0], True)
+    assert np.abs(npy(lab_l) - oracle.compute_luminance(den)).max() <= TOL
+    d = np.abs(npy(out) - oracle.modify_luminance(den, oracle.bilateral(npy(lab_l), 2.0, 0.2, 0.4)))
+    assert d.max() <= 2 * TOL, (d.max(), np.unravel_index(d.argmax(), d.shape))

@@ -504,11 +504,20 @@ def normalize_image(image: torch.Tensor, bounds: torch.Tensor) -> torch.Tensor:
 
 
 _BOUNDS_STATE: dict = {}
+_BOUNDS_LOCKS: dict = {}
+
+
+def _state_lock(locks: dict, key) -> threading.Lock:
+  """The lock of one per-(device, stream) cached state.  Host threads share the stream (the default stream is everyone's): a list
+  issued by one thread must not interleave with another thread's list on the same state (dict.setdefault is atomic)."""
+  lock = locks.get(key)
+  return lock if lock is not None else locks.setdefault(key, threading.Lock())
 
 
 def compute_image_bounds(images: Sequence[torch.Tensor], stride: int = 8) -> torch.Tensor:
   """One launch per image (tdk_image_bounds): minimum and maximum go through a persistent per-(device, stream) state of four words that is
-  idle between calls, the workgroup that draws the list's last ticket writes the result and resets it -- no init launch."""
+  idle between calls, the workgroup that draws the list's last ticket writes the result and resets it -- no init launch.  The state's
+  lock is held from the ticket count to the last launch, so lists of different host threads on one stream do not mix their tickets."""
   _require(len(images) > 0, 'images must be non-empty')
   dev = images[0].device
   for img in images:  # every image is checked before the first launch: a rejected list leaves the cached state idle
@@ -516,7 +525,7 @@ def compute_image_bounds(images: Sequence[torch.Tensor], stride: int = 8) -> tor
     _require(img.device == dev, f'image is on {img.device}, the first one on {dev}')
   bounds = torch.empty(2, dtype=torch.float32, device=dev)
   key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
-  with torch.cuda.device(dev):
+  with torch.cuda.device(dev), _state_lock(_BOUNDS_LOCKS, key):
     state = _BOUNDS_STATE.get(key)
     if state is None:
       state = _BOUNDS_STATE[key] = torch.tensor([-1, 0, 0, 0], dtype=torch.int32, device=dev)  # 0xffffffff, 0, 0, 0 (host copy: complete on return)
@@ -526,14 +535,15 @@ def compute_image_bounds(images: Sequence[torch.Tensor], stride: int = 8) -> tor
       for i, x in enumerate(xs):
         last = i == len(xs) - 1
         check(lib.tdk_image_bounds(_ptr(x), x.size(1), x.size(0), int(stride), _ptr(state), _ptr(bounds) if last else None, total, _dtype_tag(x), _stream()))
-    except Exception:
-      _BOUNDS_STATE.pop(key, None)  # a failed launch may have left tickets behind: start from a fresh state next time
+    except BaseException:  # KeyboardInterrupt included: a list cut short leaves its tickets behind
+      _BOUNDS_STATE.pop(key, None)  # start from a fresh state next time
       raise
   return bounds
 
 
 _UNIT_BOUNDS: dict = {}
 _METRICS_STATE: dict = {}
+_METRICS_LOCKS: dict = {}
 
 
 def _unit_bounds(dev: torch.device) -> torch.Tensor:
@@ -550,21 +560,22 @@ def compute_image_metrics(images: Sequence[torch.Tensor], stride: int = 8, min_g
   _require(dev.type == 'cuda', 'image must be CUDA')
   bounds = compute_image_bounds(images, stride) if rescale else None
   key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
-  acc = _METRICS_STATE.get(key)
-  if acc is None:
-    acc = _METRICS_STATE[key] = MetricsAccumulator(dev)
   for img in images:  # every image is checked before the first one is added: a bad list leaves nothing behind in the cached accumulator
     _check_rgb(img, allow_half=True)
     _require(img.device == dev, f'image is on {img.device}, the first one on {dev}')
-  acc.stride, acc.min_gray = int(stride), float(min_gray)
-  acc.bounds = bounds if bounds is not None else _unit_bounds(dev)
-  try:
-    for img in images:
-      acc.add(img)
-    return acc.finish()
-  except Exception:
-    acc.reset()
-    raise
+  with _state_lock(_METRICS_LOCKS, key):  # the accumulator's settings and sums belong to one list at a time (see _state_lock)
+    acc = _METRICS_STATE.get(key)
+    if acc is None:
+      acc = _METRICS_STATE[key] = MetricsAccumulator(dev)
+    acc.stride, acc.min_gray = int(stride), float(min_gray)
+    acc.bounds = bounds if bounds is not None else _unit_bounds(dev)
+    try:
+      for img in images:
+        acc.add(img)
+      return acc.finish()
+    except BaseException:  # KeyboardInterrupt included: no half-accumulated sums may reach the next list
+      acc.reset()
+      raise
 
 
 class MetricsAccumulator:
@@ -600,7 +611,7 @@ class MetricsAccumulator:
         else:
           check(lib.tdk_image_metrics(_ptr(x), x.size(1), x.size(0), self.stride, self.min_gray, _ptr(self.bounds), _ptr(self.acc), _ptr(metrics),
                                       _dtype_tag(x), _stream()))
-      except Exception:
+      except BaseException:
         self.reset()  # never leave half-accumulated sums behind
         raise
 
