@@ -163,7 +163,8 @@ int tdk_modify_luminance(const void* rgb, const void* lum, void* rgb_out, int64_
                          tdk_stream_t stream);
 
 /* normalize_image of the pipeline: reference torch_darktable/pipeline/util.py:8-10.
- * out[i] = (in[i] - bounds[0]) / (bounds[1] - bounds[0]) over `count` samples; bounds[2] on device. */
+ * out[i] = (in[i] - bounds[0]) / (bounds[1] - bounds[0]) over `count` samples; bounds[2] on device.  Any element-aligned
+ * buffers: four elements per thread where both are aligned to four elements, one per thread otherwise. */
 int tdk_normalize(const void* in, void* out, int64_t count, const float* bounds, int dtype, tdk_stream_t stream);
 
 /* ---- image statistics + tonemaps: reference csrc/tonemap/ (extension.cpp:172-195) */
@@ -249,7 +250,7 @@ int tdk_bilateral_rgb(const void* rgb_in, void* rgb_out, void* workspace, int wi
  * geometry and sigmas passes TDK_BILATERAL_PREPARED and skips the table launch.  Without the flag every call builds them
  * itself (the plain entry points above).  TDK_BILATERAL_GENERAL_PATH takes the four-kernel path where the tile kernel would
  * run (same bits; the GPU tests compare the two through it).  lum_in of the rgb form: the fp32 plane
- * compute_[log_]luminance(rgb_in) if the caller has it (16-byte aligned), or NULL. */
+ * compute_[log_]luminance(rgb_in) if the caller has it (any 4-byte aligned view; 16-byte aligned planes take the vector loads), or NULL. */
 #define TDK_BILATERAL_PREPARED 1u
 #define TDK_BILATERAL_GENERAL_PATH 2u
 int tdk_bilateral_prepare(void* workspace, int width, int height, float sigma_s, float sigma_r, tdk_stream_t stream);

@@ -685,7 +685,6 @@ TDK_EXPORT int tdk_bilateral_rgb_ex(const void* rgb_in, const float* lum_in, voi
   TDK_REQUIRE(width > 0 && height > 0, "Invalid dimensions");
   TDK_REQUIRE(sigma_s > 0.0f && sigma_r > 0.0f, "tdk_bilateral_rgb: sigmas must be positive");
   TDK_REQUIRE(!log_mode || eps > 0.0f, "Epsilon must be positive");
-  TDK_REQUIRE(!lum_in || tdk_aligned(lum_in, 16), "tdk_bilateral_rgb: luminance plane must be 16-byte aligned");
   TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH)) == 0, "tdk_bilateral_rgb: unknown flags 0x%x", flags);
   TDK_DISPATCH_DTYPE(dtype, T, return launch_rgb<T>(rgb_in, rgb_out, workspace, width, height, sigma_s, sigma_r, detail, log_mode, eps, dtype, flags, tdk_stream(stream), lum_in));
   return TDK_OK;

@@ -216,19 +216,34 @@ int run_modify(const void* rgb_, const void* lum_, void* out_, int64_t npix, hip
 
 // normalize_image of the pipeline (reference torch_darktable/pipeline/util.py:8-10, a torch.compile'd
 // elementwise expression): (x - bounds[0]) / (bounds[1] - bounds[0]) with the bounds on the device.
+// Four elements per thread (s4_io: 16-B fp32 / 8-B binary16 accesses) on buffers aligned to four elements; the elements past
+// the last group, or every element of an unaligned view (a frame of a batch, a slice), go through normalize_tail.
 template <typename T>
-__global__ __launch_bounds__(256) void normalize_kernel(const T* __restrict__ in, T* __restrict__ out, int64_t n, const float* __restrict__ bounds) {
+__global__ __launch_bounds__(256) void normalize_vec4(const T* __restrict__ in, T* __restrict__ out, int64_t ngroups, const float* __restrict__ bounds) {
   const float b0 = bounds[0], range = bounds[1] - bounds[0];
-  const int64_t n4 = n / 4;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n4; g += (int64_t)gridDim.x * 256) {
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256) {
     float v[4];
     s4_io<T>::load(in, (size_t)g, v);
 #pragma unroll
     for (int k = 0; k < 4; k++) v[k] = (v[k] - b0) / range;
     s4_io<T>::store(out, (size_t)g, v);
   }
-  if (blockIdx.x == 0)
-    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += 256) st(out, (size_t)i, (ld(in, (size_t)i) - b0) / range);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void normalize_tail(const T* __restrict__ in, T* __restrict__ out, int64_t first, int64_t n, const float* __restrict__ bounds) {
+  const float b0 = bounds[0], range = bounds[1] - bounds[0];
+  for (int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) st(out, (size_t)i, (ld(in, (size_t)i) - b0) / range);
+}
+
+template <typename T> int run_normalize(const T* in, T* out, int64_t n, const float* bounds, hipStream_t s) {
+  int64_t done = 0;
+  if (tdk_aligned(in, 4 * sizeof(T)) && tdk_aligned(out, 4 * sizeof(T)) && n >= 4) {
+    const int64_t ng = n / 4;
+    TDK_LAUNCH("tdk_normalize", normalize_vec4<T>, dim3(stream_grid(ng)), dim3(256), 0, s, in, out, ng, bounds);
+    done = ng * 4;
+  }
+  if (done < n) TDK_LAUNCH("tdk_normalize", normalize_tail<T>, dim3(stream_grid(n - done)), dim3(256), 0, s, in, out, done, n, bounds);
+  return TDK_OK;
 }
 
 }  // namespace
@@ -314,8 +329,6 @@ TDK_EXPORT int tdk_normalize(const void* in, void* out, int64_t count, const flo
   TDK_REQUIRE(count >= 0, "tdk_normalize: negative element count");
   if (count == 0) return TDK_OK;
   TDK_REQUIRE(in && out && bounds, "tdk_normalize: null pointer");
-  TDK_REQUIRE(tdk_aligned(in, 16) && tdk_aligned(out, 16), "tdk_normalize: buffers must be 16-byte aligned");
-  TDK_DISPATCH_DTYPE(dtype, T, TDK_LAUNCH("tdk_normalize", normalize_kernel<T>, dim3(stream_grid(count / 4 + 1)), dim3(256), 0, tdk_stream(stream),
-                                                  reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), count, bounds));
+  TDK_DISPATCH_DTYPE(dtype, T, return run_normalize<T>(reinterpret_cast<const T*>(in), reinterpret_cast<T*>(out), count, bounds, tdk_stream(stream)));
   return TDK_OK;
 }
