@@ -35,8 +35,11 @@ CXXFLAGS = ['-O3', '-std=c++17', f'--offload-arch={ARCH}', '-ffp-contract=off', 
 CXXFLAGS += os.environ.get('TDK_EXTRA_FLAGS', '').split()  # experiments: e.g. TDK_EXTRA_FLAGS=-DTDK_WIENER_SHARED_ACC=1
 
 
+HEADERS = [HERE.parent / 'include' / 'tdk_hip.h', HERE.parent / 'include' / 'tdk_hip_ext.h']
+
+
 def _inputs():
-  return sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [HERE.parent / 'include' / 'tdk_hip.h']
+  return sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + HEADERS
 
 
 def source_hash() -> str:
@@ -76,7 +79,7 @@ def _stale(target: Path, deps) -> bool:
 
 def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -> Path:
   OBJ.mkdir(exist_ok=True)
-  headers = list(CSRC.glob('*.h')) + [HERE.parent / 'include' / 'tdk_hip.h']
+  headers = list(CSRC.glob('*.h')) + HEADERS
   sources = sorted(CSRC.glob('*.hip'))
   todo = []
   objs = []

@@ -25,6 +25,7 @@
 // Progressive = SOF2 with one interleaved DC scan and one AC scan (1..63) per component; every block closes its own band
 // (EOBRUN = 1), so the block walks stay independent.
 #include "tdk_common.h"
+#include "../../include/tdk_hip_ext.h"
 
 #include <string.h>
 
@@ -455,19 +456,24 @@ __global__ __launch_bounds__(256) void jpeg_code_kernel(const uint32_t* __restri
   }
 }
 
-// device-side scalars of a scan
+// device-side scalars of a scan (pos, base: the device path's stream position and the start of the scan's segment in `out`)
 struct Scal {
   unsigned long long total_bits;
   unsigned int nbytes, nchunks, total_ff, overflow;
   unsigned long long seg_len;
+  unsigned long long pos, base;
 };
 
 // exclusive prefix sum of n uint32 (n from the host, or from *n_dev) into uint64 out[0..n]; one workgroup of 1024.
 // what: 0 = block lengths -> total_bits / nbytes / nchunks, 1 = 0xFF counts -> total_ff / seg_len
 // what = 1 also closes the stream behind this segment with EOI (the markers of a following scan overwrite it)
+// DEV (the device path): the overflow flag is the whole call's (cleared once, at its start); the segment starts at the device-resident
+// position sc->pos of `segment` (= out, room = its capacity), which what = 1 checks, records in sc->base and advances; length_out, if
+// given, receives the stream's final length or -1.
+template <bool DEV>
 __global__ __launch_bounds__(1024) void jpeg_scan_kernel(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t n_host,
                                                           Scal* __restrict__ sc, int what, uint8_t* __restrict__ segment, unsigned long long room,
-                                                          uint32_t* __restrict__ clear) {
+                                                          uint32_t* __restrict__ clear, long long* __restrict__ length_out) {
   __shared__ uint64_t wtot[16];
   __shared__ uint64_t carry_s;
   const uint32_t n = what == 0 ? n_host : sc->nchunks;
@@ -499,15 +505,28 @@ __global__ __launch_bounds__(1024) void jpeg_scan_kernel(const uint32_t* __restr
     if (what == 0) {
       clear[carry_s >> 5] = 0u;   // the dword of the padding bits
       sc->total_bits = carry_s;
-      sc->overflow = 0u;
+      if (!DEV) sc->overflow = 0u;
       sc->nbytes = (unsigned int)((carry_s + 7) >> 3);
       sc->nchunks = (sc->nbytes + 4095u) >> 12;
     } else {
       sc->total_ff = (unsigned int)carry_s;
       const unsigned long long seg = (unsigned long long)sc->nbytes + carry_s;
       sc->seg_len = seg;
-      if (seg + 2 <= room) { segment[seg] = 0xff; segment[seg + 1] = 0xd9; }
-      else sc->overflow = 1u;
+      if (DEV) {
+        const unsigned long long p = sc->pos;
+        if (!sc->overflow && p + seg + 2 <= room) {
+          segment[p + seg] = 0xff;
+          segment[p + seg + 1] = 0xd9;
+          sc->base = p;
+          sc->pos = p + seg;
+        } else {
+          sc->overflow = 1u;
+        }
+        if (length_out) *length_out = sc->overflow ? -1ll : (long long)(sc->pos + 2);
+      } else {
+        if (seg + 2 <= room) { segment[seg] = 0xff; segment[seg + 1] = 0xd9; }
+        else sc->overflow = 1u;
+      }
     }
   }
 }
@@ -516,11 +535,17 @@ __global__ __launch_bounds__(1024) void jpeg_scan_kernel(const uint32_t* __restr
 __device__ __forceinline__ uint32_t be_byte(uint32_t word, int k) { return (word >> (24 - 8 * k)) & 255u; }
 
 // SCATTER = false: ffcnt[chunk] = number of 0xFF bytes in the 4 KB chunk; true: write the chunk's bytes, stuffed, to `stream`.
-template <bool SCATTER>
+// DEV (the device path): the segment starts at sc->base (jpeg_scan_kernel<true> put it there after checking that the segment and EOI
+// fit in `cap`); after an overflow anywhere in the call nothing is written.
+template <bool SCATTER, bool DEV = false>
 __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restrict__ raw, const Scal* __restrict__ sc, uint32_t* __restrict__ ffcnt,
                                                           const uint64_t* __restrict__ ffoff, uint8_t* __restrict__ stream, unsigned long long base,
                                                           unsigned long long cap, Scal* __restrict__ sc_out) {
   __shared__ uint32_t wsum[4];
+  if (DEV) {
+    if (sc->overflow) return;
+    base = sc->base;
+  }
   const uint32_t nbytes = sc->nbytes, nchunks = sc->nchunks;
   for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const uint32_t b0 = chunk * 4096u + threadIdx.x * 16u;
@@ -562,6 +587,236 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const uint32_t* __restr
       }
     }
   }
+}
+
+// ------------------------------------------------------------------ device path: optimal tables (K.2, K.3) and markers
+// What the host knows of a scan's markers before the data exists, passed by value: the frame header (first scan only) and the SOS.
+struct MarkerArgs {
+  uint8_t head[184];   // SOI, APP0, DQT x 1 - 2, SOF0 / SOF2: at most 177 bytes
+  uint8_t sos[16];     // at most 14 bytes
+  int nhead, nsos;
+  int tmask;           // tables of the scan: bit 0 / 1 = DC luma / chroma, bit 2 / 3 = AC luma / chroma
+};
+
+template <int CTRL> __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int lane) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// minimum over the wave (all 64 lanes active), wave-uniform: DPP inside each row of 16 lanes, then the four row minima
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k) {
+  k = umin64(k, dpp_u64<0xB1>(k));    // quad_perm [1, 0, 3, 2]
+  k = umin64(k, dpp_u64<0x4E>(k));    // quad_perm [2, 3, 0, 1]
+  k = umin64(k, dpp_u64<0x141>(k));   // row_half_mirror
+  k = umin64(k, dpp_u64<0x140>(k));   // row_mirror
+  return umin64(umin64(readlane64(k, 0), readlane64(k, 16)), umin64(readlane64(k, 32), readlane64(k, 48)));
+}
+
+// LDS of one wave's table
+struct WaveTab {
+  int bits[64];      // code-size counts, all 257 symbols (K.3 works on these)
+  int start[64];     // first HUFFVAL position of each code size (symbols 0 - 255)
+  int first[17];     // first code of each length after K.3
+  int cum[18];       // first HUFFVAL position of each length after K.3
+  uint8_t vals[256];
+  int nvals;
+};
+
+// One wave per table, bit-identical to optimal_table() below.  Lane l holds symbols l, 64 + l, 128 + l, 192 + l (lane 0 also the
+// reserved symbol 256): its frequency, its group (the symbol that heads the subtree it is in) and its code size.  A K.2 step takes the
+// two wave-wide minima of the key (freq << 9) | (511 - symbol) -- the smallest frequency, ties to the larger symbol, as the host's <=
+// -- then every member of groups c1 and c2 gets one more bit and group c2 becomes c1 (the host's walk along both others[] chains).
+// K.3 and the canonical codes run on lane 0 over 64 counts; HUFFVAL, ordered by (code size, symbol), is ranked with ballots.
+// MARKERS = false (test hook): table blockIdx.x * 4 + wave of `ntables`, BITS[16] + HUFFVAL[256] to bits_vals, codes to `packed`.
+// MARKERS = true (the encoder, one workgroup): the tables of m.tmask from the scan's histograms into `packed` (the coding passes'
+// look-up), then the frame header (first scan), the DHT segments and the SOS at the stream position sc->pos of `out` -- or, if they
+// do not fit in `cap` or the call has already failed, nothing but the overflow flag.
+template <bool MARKERS>
+__global__ __launch_bounds__(256) void jpeg_tables_kernel(uint32_t* __restrict__ hist, int ntables, uint32_t* __restrict__ packed,
+                                                           uint8_t* __restrict__ bits_vals, Scal* __restrict__ sc, uint8_t* __restrict__ out,
+                                                           unsigned long long cap, MarkerArgs m) {
+  __shared__ WaveTab tl[4];
+  __shared__ int seg_off[4], sos_off, skip;
+  __shared__ unsigned long long at;
+  const int w = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+  const int table = MARKERS ? w : (int)blockIdx.x * 4 + w;
+  const bool active = MARKERS ? ((m.tmask >> w) & 1) != 0 : table < ntables;   // wave-uniform
+  WaveTab& t = tl[w];
+  t.bits[lane] = 0;
+  t.start[lane] = 0;
+  for (int i = lane; i < 256; i += 64) t.vals[i] = 0;
+  constexpr unsigned long long NONE = ~0ull;
+  unsigned long long f[5];
+  int sy[5], grp[5], cs[5];
+#pragma unroll
+  for (int j = 0; j < 5; j++) {
+    sy[j] = j < 4 ? 64 * j + lane : (lane == 0 ? 256 : -1);
+    f[j] = !active ? 0ull : j < 4 ? (unsigned long long)hist[(size_t)table * 256 + sy[j]] : (lane == 0 ? 1ull : 0ull);
+    grp[j] = sy[j];
+    cs[j] = 0;
+  }
+  __syncthreads();
+
+  if (active) {
+    for (;;) {   // K.2: at most 256 steps
+      unsigned long long k = NONE;
+#pragma unroll
+      for (int j = 0; j < 5; j++) if (f[j]) k = umin64(k, (f[j] << 9) | (unsigned long long)(511 - sy[j]));
+      const unsigned long long k1 = wave_min_u64(k);
+      const int c1 = 511 - (int)(k1 & 511);
+      k = NONE;
+#pragma unroll
+      for (int j = 0; j < 5; j++) if (f[j] && sy[j] != c1) k = umin64(k, (f[j] << 9) | (unsigned long long)(511 - sy[j]));
+      const unsigned long long k2 = wave_min_u64(k);
+      if (k2 == NONE) break;
+      const int c2 = 511 - (int)(k2 & 511);
+#pragma unroll
+      for (int j = 0; j < 5; j++) {
+        if (sy[j] == c1) f[j] += k2 >> 9;
+        if (sy[j] == c2) f[j] = 0;
+        if (grp[j] == c1 || grp[j] == c2) { cs[j]++; grp[j] = c1; }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      if (cs[j] > 0) {
+        atomicAdd(&t.bits[cs[j] < 63 ? cs[j] : 63], 1);
+        if (sy[j] < 256 && cs[j] <= 63) atomicAdd(&t.start[cs[j]], 1);
+      }
+    }
+  }
+  __syncthreads();
+  // every wave has consumed its counts (the K.2 loop above): the next scan's histogram pass starts from zero
+  if (MARKERS) for (int i = threadIdx.x; i < 1024; i += 256) hist[i] = 0u;
+
+  if (active) {
+    if (lane == 0) {   // K.3 (figure K.3), then the first code and first HUFFVAL position of every length
+      int* b = t.bits;
+      for (int i = 63; i > 16; i--) {
+        while (b[i] > 0) {
+          int j = i - 2;
+          while (b[j] == 0) j--;
+          b[i] -= 2;
+          b[i - 1]++;
+          b[j + 1] += 2;
+          b[j]--;
+        }
+      }
+      int i = 16;
+      while (i > 0 && b[i] == 0) i--;
+      if (i > 0) b[i]--;
+      int code = 0, k = 0;
+      for (int l = 1; l <= 16; l++) {
+        t.first[l] = code;
+        t.cum[l] = k;
+        k += b[l];
+        code = (code + b[l]) << 1;
+      }
+      t.cum[17] = k;
+    }
+    // exclusive prefix of the code-size counts: where each code size starts in HUFFVAL
+    const int v = t.start[lane];
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    t.start[lane] = incl - v;
+    if (lane == 63) t.nvals = incl;
+  }
+  __syncthreads();
+
+  if (active) {
+    // HUFFVAL position of each symbol: code size first, then symbol (lanes in order within a group of 64 symbols)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      bool pend = cs[j] > 0 && cs[j] <= 63;
+      uint32_t pk = 0;
+      unsigned long long todo = __ballot(pend);
+      while (todo) {
+        const int L = __builtin_amdgcn_readlane(cs[j], (int)__builtin_ctzll(todo));
+        const bool mine = pend && cs[j] == L;
+        const unsigned long long mm = __ballot(mine);
+        const int base = t.start[L];
+        if (mine) {
+          const int r = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+          t.vals[r] = (uint8_t)sy[j];
+          int l = 1;
+          while (l < 16 && t.cum[l + 1] <= r) l++;
+          pk = ((uint32_t)(t.first[l] + r - t.cum[l]) << 8) | (uint32_t)l;
+          pend = false;
+        }
+        if (lane == 0) t.start[L] = base + __popcll(mm);
+        todo = __ballot(pend);
+      }
+      packed[(size_t)table * 256 + 64 * j + lane] = pk;
+    }
+  }
+  __syncthreads();
+
+  if (!MARKERS) {
+    if (active) {
+      uint8_t* bv = bits_vals + (size_t)table * 272;
+      if (lane < 16) bv[lane] = (uint8_t)t.bits[lane + 1];
+      for (int i = lane; i < 256; i += 64) bv[16 + i] = t.vals[i];
+    }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    int o = m.nhead;
+    for (int q = 0; q < 4; q++) {   // DHT order of the host path: DC luma, AC luma, DC chroma, AC chroma
+      const int tw = (q & 1) * 2 + (q >> 1);
+      if ((m.tmask >> tw) & 1) {
+        seg_off[tw] = o;
+        o += 21 + tl[tw].nvals;
+      }
+    }
+    sos_off = o;
+    const unsigned long long p = sc->pos, total = (unsigned long long)(o + m.nsos);
+    if (sc->overflow || p + total > cap) {
+      sc->overflow = 1u;
+      skip = 1;
+    } else {
+      skip = 0;
+      at = p;
+      sc->pos = p + total;
+    }
+  }
+  __syncthreads();
+  if (skip) return;
+  uint8_t* dst = out + at;
+  for (int i = threadIdx.x; i < m.nhead; i += 256) dst[i] = m.head[i];
+  for (int i = threadIdx.x; i < m.nsos; i += 256) dst[sos_off + i] = m.sos[i];
+  if (active) {
+    const int nv = t.nvals, len = 19 + nv;
+    uint8_t* d = dst + seg_off[w];
+    for (int i = lane; i < 21 + nv; i += 64) {
+      uint32_t b;
+      if (i == 0) b = 0xffu;
+      else if (i == 1) b = 0xc4u;
+      else if (i == 2) b = (uint32_t)(len >> 8);
+      else if (i == 3) b = (uint32_t)(len & 255);
+      else if (i == 4) b = (uint32_t)(((w >> 1) << 4) | (w & 1));
+      else if (i < 21) b = (uint32_t)t.bits[i - 4];
+      else b = t.vals[i - 21];
+      d[i] = (uint8_t)b;
+    }
+  }
+}
+
+// The device path's per-call reset: histograms, position and overflow flag back to zero, so that every call -- and every replay of a
+// captured call -- starts clean.  A kernel, not hipMemsetAsync: captured in a graph, the memset node reset the state for the first
+// replay but not for the second.
+__global__ __launch_bounds__(256) void jpeg_reset_kernel(uint32_t* __restrict__ hist, Scal* __restrict__ sc) {
+  for (int i = threadIdx.x; i < 1024; i += 256) hist[i] = 0u;
+  if (threadIdx.x == 0) *sc = Scal{};
 }
 
 // ------------------------------------------------------------------ host: tables, markers, orchestration
@@ -710,9 +965,72 @@ template <int SUB> int launch_fdct(const uint8_t* img, uint32_t* coef, const Geo
   return TDK_OK;
 }
 
+int launch_fdct_sub(int subsampling, const uint8_t* img, uint32_t* coef, const Geo& g, const Quant& q, hipStream_t st) {
+  return subsampling == 0 ? launch_fdct<0>(img, coef, g, q, st) : subsampling == 1 ? launch_fdct<1>(img, coef, g, q, st) : launch_fdct<2>(img, coef, g, q, st);
+}
+
+void quant_tables(int quality, uint8_t qt[2][64], Quant& q) {
+  scaled_table(Q_LUMA, quality, qt[0]);
+  scaled_table(Q_CHROMA, quality, qt[1]);
+  for (int t = 0; t < 2; t++)
+    for (int i = 0; i < 64; i++) q.rq[t][i] = (float)(1.0 / ((double)qt[t][i] * AAN[i >> 3] * AAN[i & 7] * 8.0));
+}
+
+// SOI, APP0 (JFIF), DQT, SOF0 / SOF2
+Bytes frame_header(const Geo& g, const uint8_t qt[2][64], int progressive, int width, int height) {
+  Bytes hd;
+  hd.u16(0xffd8);
+  hd.u16(0xffe0); hd.u16(16);
+  for (const char ch : {'J', 'F', 'I', 'F', '\0'}) hd.u8(ch);
+  hd.u16(0x0101); hd.u8(0); hd.u16(1); hd.u16(1); hd.u8(0); hd.u8(0);
+  for (int t = 0; t < (g.ncomp == 1 ? 1 : 2); t++) {
+    hd.u16(0xffdb); hd.u16(67); hd.u8(t);
+    for (int k = 0; k < 64; k++) hd.u8(qt[t][zz_of(k)]);
+  }
+  hd.u16(progressive ? 0xffc2 : 0xffc0);
+  hd.u16(8 + 3 * g.ncomp); hd.u8(8); hd.u16(height); hd.u16(width); hd.u8(g.ncomp);
+  for (int c = 0; c < g.ncomp; c++) { hd.u8(c + 1); hd.u8(((c == 0 ? g.hs0 : 1) << 4) | 1); hd.u8(c ? 1 : 0); }
+  return hd;
+}
+
+struct ScanPlan { int ns, comp0, ss, se; };
+
+std::vector<ScanPlan> scan_plan(const Geo& g, int progressive) {
+  std::vector<ScanPlan> plan;
+  if (!progressive) plan.push_back({g.ncomp, 0, 0, 63});
+  else {
+    plan.push_back({g.ncomp, 0, 0, 0});
+    for (int c = 0; c < g.ncomp; c++) plan.push_back({1, c, 1, 63});
+  }
+  return plan;
+}
+
+ScanDesc scan_desc(const Geo& g, const ScanPlan& p) {
+  ScanDesc sc;
+  sc.ns = p.ns; sc.comp0 = p.comp0; sc.ss = p.ss; sc.se = p.se;
+  if (p.ns > 1) sc.nscan = (long long)g.nmcux * g.nmcuy * (g.hs0 + 2);
+  else sc.nscan = (long long)g.nbx_real[p.comp0] * g.nby_real;
+  sc.chunk = p.ns > 1 ? 64 * (g.hs0 + 2) : 256;
+  return sc;
+}
+
+void put_sos(Bytes& b, const ScanPlan& p) {
+  b.u16(0xffda);
+  b.u16(6 + 2 * p.ns);
+  b.u8(p.ns);
+  for (int i = 0; i < p.ns; i++) { const int c = p.comp0 + i; b.u8(c + 1); b.u8(c ? 0x11 : 0x00); }
+  b.u8(p.ss);
+  b.u8(p.se);
+  b.u8(0);
+}
+
 // byte positions inside a scan are 32-bit on the device: the worst-case stream of the frame has to stay below 4 GB (about 1.2
 // gigapixels at 4:2:2; JPEG itself stops at 65 535 x 65 535)
 bool geo_supported(const Geo& g) { return (unsigned long long)g.nblocks * MAX_BLOCK_BYTES < 0xf0000000ull; }
+
+bool geometry_ok(int width, int height, int subsampling) {
+  return width > 0 && height > 0 && width <= 65535 && height <= 65535 && subsampling >= 0 && subsampling <= 2;
+}
 
 }  // namespace
 
@@ -751,38 +1069,13 @@ TDK_EXPORT int tdk_jpeg_encode(const void* image, int width, int height, int inp
 
   uint8_t qt[2][64];
   Quant q;
-  scaled_table(Q_LUMA, quality, qt[0]);
-  scaled_table(Q_CHROMA, quality, qt[1]);
-  for (int t = 0; t < 2; t++)
-    for (int i = 0; i < 64; i++) q.rq[t][i] = (float)(1.0 / ((double)qt[t][i] * AAN[i >> 3] * AAN[i & 7] * 8.0));
+  quant_tables(quality, qt, q);
 
-  int rc = subsampling == 0 ? launch_fdct<0>(reinterpret_cast<const uint8_t*>(image), coef, g, q, st)
-         : subsampling == 1 ? launch_fdct<1>(reinterpret_cast<const uint8_t*>(image), coef, g, q, st)
-                            : launch_fdct<2>(reinterpret_cast<const uint8_t*>(image), coef, g, q, st);
+  int rc = launch_fdct_sub(subsampling, reinterpret_cast<const uint8_t*>(image), coef, g, q, st);
   if (rc != TDK_OK) return rc;
 
-  // frame header
-  Bytes hd;
-  hd.u16(0xffd8);
-  hd.u16(0xffe0); hd.u16(16);
-  for (const char ch : {'J', 'F', 'I', 'F', '\0'}) hd.u8(ch);
-  hd.u16(0x0101); hd.u8(0); hd.u16(1); hd.u16(1); hd.u8(0); hd.u8(0);
-  for (int t = 0; t < (g.ncomp == 1 ? 1 : 2); t++) {
-    hd.u16(0xffdb); hd.u16(67); hd.u8(t);
-    for (int k = 0; k < 64; k++) hd.u8(qt[t][zz_of(k)]);
-  }
-  hd.u16(progressive ? 0xffc2 : 0xffc0);
-  hd.u16(8 + 3 * g.ncomp); hd.u8(8); hd.u16(height); hd.u16(width); hd.u8(g.ncomp);
-  for (int c = 0; c < g.ncomp; c++) { hd.u8(c + 1); hd.u8(((c == 0 ? g.hs0 : 1) << 4) | 1); hd.u8(c ? 1 : 0); }
-
-  // scans
-  struct ScanPlan { int ns, comp0, ss, se; };
-  std::vector<ScanPlan> plan;
-  if (!progressive) plan.push_back({g.ncomp, 0, 0, 63});
-  else {
-    plan.push_back({g.ncomp, 0, 0, 0});
-    for (int c = 0; c < g.ncomp; c++) plan.push_back({1, c, 1, 63});
-  }
+  const Bytes hd = frame_header(g, qt, progressive, width, height);
+  const std::vector<ScanPlan> plan = scan_plan(g, progressive);
   std::vector<Bytes> keep;  // host sources of the asynchronous copies stay alive until the last synchronisation
   keep.reserve(plan.size() * 2 + 2);
   std::vector<std::vector<uint32_t>> keep_tabs;
@@ -799,11 +1092,7 @@ TDK_EXPORT int tdk_jpeg_encode(const void* image, int width, int height, int inp
   Scal hs;
   for (size_t si = 0; si < plan.size(); si++) {
     const ScanPlan& p = plan[si];
-    ScanDesc sc;
-    sc.ns = p.ns; sc.comp0 = p.comp0; sc.ss = p.ss; sc.se = p.se;
-    if (p.ns > 1) sc.nscan = (long long)g.nmcux * g.nmcuy * (g.hs0 + 2);
-    else sc.nscan = (long long)g.nbx_real[p.comp0] * g.nby_real;
-    sc.chunk = p.ns > 1 ? 64 * (g.hs0 + 2) : 256;
+    const ScanDesc sc = scan_desc(g, p);
     const unsigned nwg = (unsigned)tdk_div_up64(sc.nscan, sc.chunk);
 
     TDK_HIP_CALL(hipMemsetAsync(hist, 0, 4096, st), "tdk_jpeg_encode: memset");
@@ -829,13 +1118,7 @@ TDK_EXPORT int tdk_jpeg_encode(const void* image, int width, int height, int inp
       if (p.ss == 0) { optimal_table(hh + t * 256, tb[t]); put_dht(pending, 0, t, tb[t]); memcpy(&packed[t * 256], tb[t].packed, 1024); }
       if (p.se > 0) { optimal_table(hh + (2 + t) * 256, tb[2 + t]); put_dht(pending, 1, t, tb[2 + t]); memcpy(&packed[(2 + t) * 256], tb[2 + t].packed, 1024); }
     }
-    pending.u16(0xffda);
-    pending.u16(6 + 2 * p.ns);
-    pending.u8(p.ns);
-    for (int i = 0; i < p.ns; i++) { const int c = p.comp0 + i; pending.u8(c + 1); pending.u8(c ? 0x11 : 0x00); }
-    pending.u8(p.ss);
-    pending.u8(p.se);
-    pending.u8(0);
+    put_sos(pending, p);
     TDK_REQUIRE(pos + pending.v.size() + 2 <= L.stream_cap, "tdk_jpeg_encode: stream larger than the workspace");
     keep.push_back(pending);
     TDK_HIP_CALL(hipMemcpyAsync(out + pos, keep.back().v.data(), keep.back().v.size(), hipMemcpyHostToDevice, st), "tdk_jpeg_encode: header copy");
@@ -844,11 +1127,12 @@ TDK_EXPORT int tdk_jpeg_encode(const void* image, int width, int height, int inp
     TDK_HIP_CALL(hipMemcpyAsync(tabs, packed.data(), 4096, hipMemcpyHostToDevice, st), "tdk_jpeg_encode: table copy");
 
     TDK_LAUNCH("tdk_jpeg(lengths)", (jpeg_code_kernel<LEN>), dim3(nwg), dim3(256), 0, st, coef, g, sc, hist, tabs, lens, wgsum, wgoff, raw);
-    TDK_LAUNCH("tdk_jpeg(scan)", jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, wgsum, wgoff, (uint32_t)nwg, scal, 0, out, 0ull, raw);
+    TDK_LAUNCH("tdk_jpeg(scan)", jpeg_scan_kernel<false>, dim3(1), dim3(1024), 0, st, wgsum, wgoff, (uint32_t)nwg, scal, 0, out, 0ull, raw, nullptr);
     TDK_LAUNCH("tdk_jpeg(write)", (jpeg_code_kernel<WRITE>), dim3(nwg), dim3(256), 0, st, coef, g, sc, hist, tabs, lens, wgsum, wgoff, raw);
     TDK_LAUNCH("tdk_jpeg(count ff)", (jpeg_stuff_kernel<false>), dim3((unsigned)persistent), dim3(256), 0, st, raw, scal, ffcnt, ffoff, out,
                (unsigned long long)pos, (unsigned long long)(L.stream_cap - 2), scal);
-    TDK_LAUNCH("tdk_jpeg(scan)", jpeg_scan_kernel, dim3(1), dim3(1024), 0, st, ffcnt, ffoff, 0u, scal, 1, out + pos, (unsigned long long)(L.stream_cap - pos), raw);
+    TDK_LAUNCH("tdk_jpeg(scan)", jpeg_scan_kernel<false>, dim3(1), dim3(1024), 0, st, ffcnt, ffoff, 0u, scal, 1, out + pos, (unsigned long long)(L.stream_cap - pos), raw,
+               nullptr);
     TDK_LAUNCH("tdk_jpeg(stuff)", (jpeg_stuff_kernel<true>), dim3((unsigned)persistent), dim3(256), 0, st, raw, scal, ffcnt, ffoff, out,
                (unsigned long long)pos, (unsigned long long)(L.stream_cap - 2), scal);
   }
@@ -858,6 +1142,110 @@ TDK_EXPORT int tdk_jpeg_encode(const void* image, int width, int height, int inp
   pos += (size_t)hs.seg_len;
   *length = pos + 2;  // EOI is already there (jpeg_scan_kernel)
   drain.armed = false;  // the stream was synchronised two lines up
+  return TDK_OK;
+}
+
+// ------------------------------------------------------------------ device path (include/tdk_hip_ext.h)
+TDK_EXPORT int tdk_ext_abi_version(void) { return TDK_EXT_ABI_VERSION; }
+
+// the workspace of tdk_jpeg_encode without its stream region: the device path stuffs straight into the caller's buffer
+TDK_EXPORT size_t tdk_jpeg_device_workspace_bytes(int width, int height, int subsampling) {
+  if (!geometry_ok(width, height, subsampling)) return 0;
+  Geo g;
+  make_geo(width, height, 3, subsampling, g);
+  return geo_supported(g) ? make_layout(g).stream : 0;
+}
+
+TDK_EXPORT size_t tdk_jpeg_device_max_stream_bytes(int width, int height, int subsampling, int progressive) {
+  if (!geometry_ok(width, height, subsampling) || progressive < 0 || progressive > 1) return 0;
+  Geo g;
+  make_geo(width, height, 3, subsampling, g);
+  return geo_supported(g) ? make_layout(g).stream_cap : 0;
+}
+
+TDK_EXPORT int tdk_jpeg_encode_device(const void* image, int width, int height, int input_format, int quality, int subsampling, int progressive,
+                                      void* workspace, uint8_t* out, size_t out_capacity, int64_t* length_dev, tdk_stream_t stream) {
+  TDK_REQUIRE(image && workspace && length_dev && (out || out_capacity == 0), "tdk_jpeg_encode_device: null pointer");  // no room: -1
+  TDK_REQUIRE(width > 0 && height > 0 && width <= 65535 && height <= 65535, "tdk_jpeg_encode_device: image %dx%d outside 1..65535", width, height);
+  TDK_REQUIRE(input_format >= 0 && input_format <= 3, "Invalid input format");
+  TDK_REQUIRE(subsampling >= 0 && subsampling <= 2, "Invalid subsampling");
+  TDK_REQUIRE(quality >= 1 && quality <= 100, "tdk_jpeg_encode_device: quality %d outside 1..100", quality);
+  TDK_REQUIRE(progressive == 0 || progressive == 1, "tdk_jpeg_encode_device: progressive must be 0 or 1");
+  TDK_REQUIRE(tdk_aligned(workspace, 256), "tdk_jpeg_encode_device: workspace must be 256-byte aligned");
+  TDK_REQUIRE(tdk_aligned(length_dev, 8), "tdk_jpeg_encode_device: length_dev must be 8-byte aligned");
+  Geo g;
+  make_geo(width, height, input_format, subsampling, g);
+  TDK_REQUIRE(geo_supported(g), "tdk_jpeg_encode_device: image %dx%d too large (worst-case stream beyond 4 GB)", width, height);
+  const Layout L = make_layout(g);
+  uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
+  uint32_t* coef = reinterpret_cast<uint32_t*>(ws + L.coef);
+  uint16_t* lens = reinterpret_cast<uint16_t*>(ws + L.lens);
+  uint32_t* wgsum = reinterpret_cast<uint32_t*>(ws + L.wgsum);
+  uint64_t* wgoff = reinterpret_cast<uint64_t*>(ws + L.wgoff);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.hist);
+  uint32_t* tabs = reinterpret_cast<uint32_t*>(ws + L.tabs);
+  Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
+  uint32_t* ffcnt = reinterpret_cast<uint32_t*>(ws + L.ffcnt);
+  uint64_t* ffoff = reinterpret_cast<uint64_t*>(ws + L.ffoff);
+  uint32_t* raw = reinterpret_cast<uint32_t*>(ws + L.raw);
+  const unsigned long long cap = (unsigned long long)out_capacity;
+  hipStream_t st = tdk_stream(stream);
+
+  uint8_t qt[2][64];
+  Quant q;
+  quant_tables(quality, qt, q);
+  MarkerArgs m;
+  memset(&m, 0, sizeof m);
+  const Bytes hd = frame_header(g, qt, progressive, width, height);
+  TDK_REQUIRE(hd.v.size() <= sizeof m.head, "tdk_jpeg_encode_device: frame header of %zu bytes", hd.v.size());
+  memcpy(m.head, hd.v.data(), hd.v.size());
+  m.nhead = (int)hd.v.size();
+
+  TDK_LAUNCH("tdk_jpeg(reset)", jpeg_reset_kernel, dim3(1), dim3(256), 0, st, hist, scal);
+  int rc = launch_fdct_sub(subsampling, reinterpret_cast<const uint8_t*>(image), coef, g, q, st);
+  if (rc != TDK_OK) return rc;
+  const std::vector<ScanPlan> plan = scan_plan(g, progressive);
+  const int persistent = tdk_device_cus() * 4;
+  for (size_t si = 0; si < plan.size(); si++) {
+    const ScanPlan& p = plan[si];
+    const ScanDesc sc = scan_desc(g, p);
+    const unsigned nwg = (unsigned)tdk_div_up64(sc.nscan, sc.chunk);
+    const bool last = si + 1 == plan.size();
+    m.tmask = 0;
+    for (int i = 0; i < p.ns; i++) {
+      const int t = (p.comp0 + i) ? 1 : 0;
+      if (p.ss == 0) m.tmask |= 1 << t;
+      if (p.se > 0) m.tmask |= 4 << t;
+    }
+    Bytes sos;
+    put_sos(sos, p);
+    memcpy(m.sos, sos.v.data(), sos.v.size());
+    m.nsos = (int)sos.v.size();
+
+    const unsigned nhist = nwg < (unsigned)(persistent / 2) ? nwg : (unsigned)(persistent / 2);
+    TDK_LAUNCH("tdk_jpeg(histogram)", (jpeg_code_kernel<HIST>), dim3(nhist), dim3(256), 0, st, coef, g, sc, hist, tabs, lens, wgsum, wgoff, raw);
+    TDK_LAUNCH("tdk_jpeg(tables)", jpeg_tables_kernel<true>, dim3(1), dim3(256), 0, st, hist, 4, tabs, nullptr, scal, out, cap, m);
+    m.nhead = 0;  // the frame header goes in front of the first scan only
+    TDK_LAUNCH("tdk_jpeg(lengths)", (jpeg_code_kernel<LEN>), dim3(nwg), dim3(256), 0, st, coef, g, sc, hist, tabs, lens, wgsum, wgoff, raw);
+    TDK_LAUNCH("tdk_jpeg(scan)", jpeg_scan_kernel<true>, dim3(1), dim3(1024), 0, st, wgsum, wgoff, (uint32_t)nwg, scal, 0, out, cap, raw, nullptr);
+    TDK_LAUNCH("tdk_jpeg(write)", (jpeg_code_kernel<WRITE>), dim3(nwg), dim3(256), 0, st, coef, g, sc, hist, tabs, lens, wgsum, wgoff, raw);
+    TDK_LAUNCH("tdk_jpeg(count ff)", (jpeg_stuff_kernel<false>), dim3((unsigned)persistent), dim3(256), 0, st, raw, scal, ffcnt, ffoff, out, 0ull, cap, scal);
+    TDK_LAUNCH("tdk_jpeg(scan)", jpeg_scan_kernel<true>, dim3(1), dim3(1024), 0, st, ffcnt, ffoff, 0u, scal, 1, out, cap, raw,
+               last ? reinterpret_cast<long long*>(length_dev) : nullptr);
+    TDK_LAUNCH("tdk_jpeg(stuff)", (jpeg_stuff_kernel<true, true>), dim3((unsigned)persistent), dim3(256), 0, st, raw, scal, ffcnt, ffoff, out, 0ull,
+               cap, scal);
+  }
+  return TDK_OK;
+}
+
+// test hook: the device tables of `ntables` histograms (four per workgroup; the workgroups share nothing)
+TDK_EXPORT int tdk_jpeg_huffman_tables(const uint32_t* counts_dev, int ntables, uint8_t* bits_vals_dev, uint32_t* packed_dev, tdk_stream_t stream) {
+  TDK_REQUIRE(counts_dev && bits_vals_dev && packed_dev, "tdk_jpeg_huffman_tables: null pointer");
+  TDK_REQUIRE(ntables >= 1 && ntables <= (1 << 20), "tdk_jpeg_huffman_tables: ntables %d outside 1..2^20", ntables);
+  MarkerArgs m;
+  memset(&m, 0, sizeof m);
+  TDK_LAUNCH("tdk_jpeg(tables)", jpeg_tables_kernel<false>, dim3((unsigned)tdk_div_up(ntables, 4)), dim3(256), 0, tdk_stream(stream), const_cast<uint32_t*>(counts_dev), ntables,
+             packed_dev, bits_vals_dev, nullptr, nullptr, 0ull, m);
   return TDK_OK;
 }
 

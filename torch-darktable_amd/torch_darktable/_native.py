@@ -94,6 +94,15 @@ SIGNATURES = {
   'tdk_jpeg_coefficients': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_ext.h, the entry points beyond the reference's surface
+EXT_SIGNATURES = {
+  'tdk_ext_abi_version': (c_int, []),
+  'tdk_jpeg_device_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_jpeg_device_max_stream_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_jpeg_encode_device': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+  'tdk_jpeg_huffman_tables': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 TDK_F32, TDK_F16 = 0, 1
 
 
@@ -104,12 +113,15 @@ def load() -> C.CDLL:
       'torch_darktable has no CPU or pure-PyTorch fallback.'
     )
   lib = C.CDLL(str(_LIB_PATH))
-  for name, (restype, argtypes) in SIGNATURES.items():
-    fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
-    fn.restype = restype
-    fn.argtypes = argtypes
+  for table in (SIGNATURES, EXT_SIGNATURES):
+    for name, (restype, argtypes) in table.items():
+      fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
+      fn.restype = restype
+      fn.argtypes = argtypes
   if lib.tdk_abi_version() != 4:
     raise ImportError(f'libtdk_hip.so ABI version {lib.tdk_abi_version()} != 4')
+  if lib.tdk_ext_abi_version() != 1:
+    raise ImportError(f'libtdk_hip.so extension ABI version {lib.tdk_ext_abi_version()} != 1')
   return lib
 
 
