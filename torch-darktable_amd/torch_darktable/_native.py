@@ -103,6 +103,13 @@ EXT_SIGNATURES = {
   'tdk_jpeg_huffman_tables': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_denoise.h, the denoisers the reference does not have
+DENOISE_SIGNATURES = {
+  'tdk_denoise_abi_version': (c_int, []),
+  'tdk_nlmeans': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+  'tdk_nlmeans_lds_bytes': (c_size_t, [c_int, c_int, c_int]),
+}
+
 TDK_F32, TDK_F16 = 0, 1
 
 
@@ -113,7 +120,7 @@ def load() -> C.CDLL:
       'torch_darktable has no CPU or pure-PyTorch fallback.'
     )
   lib = C.CDLL(str(_LIB_PATH))
-  for table in (SIGNATURES, EXT_SIGNATURES):
+  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
       fn.restype = restype
@@ -122,6 +129,8 @@ def load() -> C.CDLL:
     raise ImportError(f'libtdk_hip.so ABI version {lib.tdk_abi_version()} != 4')
   if lib.tdk_ext_abi_version() != 1:
     raise ImportError(f'libtdk_hip.so extension ABI version {lib.tdk_ext_abi_version()} != 1')
+  if lib.tdk_denoise_abi_version() != 1:
+    raise ImportError(f'libtdk_hip.so denoise ABI version {lib.tdk_denoise_abi_version()} != 1')
   return lib
 
 
