@@ -1,6 +1,8 @@
 """packed raw bytes -> uint8 RGB: decode -> [white balance] -> demosaic -> [post-process] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> orientation
-(reference torch_darktable/pipeline/image_processor.py).
+(reference torch_darktable/pipeline/image_processor.py).  `process_resized` / `process_image_set_resized` put the
+antialiased scaler to `final_size` between the tone mapper and the orientation; `process` / `process_image_set` ignore
+`resize_width`, as the reference does.
 
 Everything between the byte upload and the uint8 result stays on the device: bounds / metrics
 and their moving averages are device tensors, no `.item()` anywhere, so one process can keep
@@ -15,6 +17,7 @@ from .. import tonemap as _tonemap
 from ..bayer import BayerPattern, PackedFormat
 from ..denoise import Wiener
 from ..local_contrast import Bilateral
+from ..resample import Resize
 from ..white_balance import apply_white_balance
 from .camera_settings import CameraSettings
 from .config import Debayer, ImageProcessingSettings, ToneMapper
@@ -55,6 +58,7 @@ class ImageProcessor:
         self.rcd_workspace = _debayer.RCD(device, image_size, bayer_pattern)
         self.wiener_workspace = Wiener(device, image_size)
         self._build_tunable_workspaces(settings)
+        self._build_resize_workspace()
         self.white_balance = torch.tensor(white_balance, device=device, dtype=torch.float32) if white_balance is not None else None
 
     def _build_tunable_workspaces(self, s: ImageProcessingSettings, which=('bilateral', 'ppg', 'postprocess')) -> None:
@@ -66,6 +70,17 @@ class ImageProcessor:
             self.postprocess_workspace = _debayer.PostProcess(
                 self.device, self.image_size, self.bayer_pattern, color_smoothing_passes=s.color_smoothing_passes,
                 green_eq_local=False, green_eq_global=True, green_eq_threshold=s.green_eq_threshold)
+
+    def _build_resize_workspace(self) -> None:
+        """The scaler of process_resized (None: resize_width == 0).  A resize_width the scaler cannot serve (beyond 16:1) is
+        reported by process_resized, not here: every other call ignores resize_width."""
+        self.resize_workspace: Resize | None = None
+        self._resize_error: ValueError | None = None
+        if self.settings.resize_width != 0:
+            try:
+                self.resize_workspace = Resize(self.device, self.image_size, self.final_size)
+            except ValueError as e:
+                self._resize_error = e
 
     def __repr__(self) -> str:
         wb = 'None' if self.white_balance is None else '({:.3f}, {:.3f}, {:.3f})'.format(*self.white_balance.tolist())
@@ -94,6 +109,8 @@ class ImageProcessor:
         if changed('color_smoothing_passes', 'green_eq_threshold'):
             stale.append('postprocess')
         self._build_tunable_workspaces(settings, tuple(stale))
+        if changed('resize_width'):
+            self._build_resize_workspace()
 
     @property
     def final_size(self) -> tuple[int, int]:
@@ -203,6 +220,21 @@ class ImageProcessor:
 
     def process_image_set(self, image_set_bytes: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         """One synchronised set of cameras: shared bounds / metrics (moving-averaged across calls)."""
+        return self._process_image_set(image_set_bytes, resized=False)
+
+    def process_resized(self, bytes: torch.Tensor, image_name: str) -> torch.Tensor:
+        """`process`, scaled to `final_size` (longest edge = settings.resize_width) before the orientation: the result has
+        transformed_size(final_size, transform).  resize_width == 0: what `process` returns."""
+        return self.process_image_set_resized({image_name: bytes})[image_name]
+
+    def process_image_set_resized(self, image_set_bytes: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
+        """`process_image_set` with every tone-mapped uint8 frame scaled to `final_size` (antialiased, `Resize`) before its
+        orientation; bounds and metrics are those of the full-size frames, updated exactly as `process_image_set` does."""
+        return self._process_image_set(image_set_bytes, resized=True)
+
+    def _process_image_set(self, image_set_bytes: dict[str, torch.Tensor], resized: bool) -> dict[str, torch.Tensor]:
+        if resized and self._resize_error is not None:
+            raise self._resize_error
         names = list(image_set_bytes.keys())
         ema = self.settings.moving_average
         rgb = [self.load_image(b) for b in image_set_bytes.values()]
@@ -213,4 +245,6 @@ class ImageProcessor:
         metrics = acc.finish()
         self.metrics = lerp(self.metrics if self.metrics is not None else metrics, metrics, ema)
         mapped = [self.tonemap(img, self.metrics) for img in rgb]
+        if resized and self.resize_workspace is not None:
+            mapped = [self.resize_workspace.process(img) for img in mapped]
         return {name: self.transform(img, name) for name, img in zip(names, mapped)}
