@@ -117,8 +117,17 @@ RESAMPLE_SIGNATURES = {
   'tdk_resample_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_warp.h, the parametric warp (map: a host pointer to 18 floats)
+WARP_SIGNATURES = {
+  'tdk_warp_abi_version': (c_int, []),
+  'tdk_warp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
+  'tdk_warp_coordinates': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+  'tdk_warp_lds_bytes': (c_size_t, [c_int, c_int, c_int]),
+}
+
 TDK_F32, TDK_F16 = 0, 1
-TDK_U8 = 2  # include/tdk_hip_resample.h: taken by tdk_resample only
+TDK_U8 = 2  # include/tdk_hip_resample.h: taken by tdk_resample and tdk_warp only
+TDK_WARP_DIRECT = 1  # include/tdk_hip_warp.h: flags of tdk_warp
 
 
 def load() -> C.CDLL:
@@ -128,7 +137,7 @@ def load() -> C.CDLL:
       'torch_darktable has no CPU or pure-PyTorch fallback.'
     )
   lib = C.CDLL(str(_LIB_PATH))
-  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES):
+  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
       fn.restype = restype
@@ -141,6 +150,8 @@ def load() -> C.CDLL:
     raise ImportError(f'libtdk_hip.so denoise ABI version {lib.tdk_denoise_abi_version()} != 1')
   if lib.tdk_resample_abi_version() != 1:
     raise ImportError(f'libtdk_hip.so resample ABI version {lib.tdk_resample_abi_version()} != 1')
+  if lib.tdk_warp_abi_version() != 1:
+    raise ImportError(f'libtdk_hip.so warp ABI version {lib.tdk_warp_abi_version()} != 1')
   return lib
 
 
