@@ -125,9 +125,20 @@ WARP_SIGNATURES = {
   'tdk_warp_lds_bytes': (c_size_t, [c_int, c_int, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_raw.h, the sensor correction (black, scale: host pointers to 4 floats each)
+RAW_SIGNATURES = {
+  'tdk_raw_abi_version': (c_int, []),
+  'tdk_raw_prepare': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p,
+                              c_int, c_int, c_void_p, c_int, c_void_p]),
+  'tdk_raw_prepare_lds_bytes': (c_size_t, [c_int, c_int]),
+}
+
 TDK_F32, TDK_F16 = 0, 1
 TDK_U8 = 2  # include/tdk_hip_resample.h: taken by tdk_resample and tdk_warp only
 TDK_WARP_DIRECT = 1  # include/tdk_hip_warp.h: flags of tdk_warp
+# include/tdk_hip_raw.h: src_format and defects of tdk_raw_prepare
+TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, TDK_RAW_F32, TDK_RAW_F16 = 0, 1, 2, 3, 4
+TDK_RAW_HOT, TDK_RAW_DEAD = 1, 2
 
 
 def load() -> C.CDLL:
@@ -137,7 +148,7 @@ def load() -> C.CDLL:
       'torch_darktable has no CPU or pure-PyTorch fallback.'
     )
   lib = C.CDLL(str(_LIB_PATH))
-  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES):
+  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
       fn.restype = restype
@@ -152,6 +163,8 @@ def load() -> C.CDLL:
     raise ImportError(f'libtdk_hip.so resample ABI version {lib.tdk_resample_abi_version()} != 1')
   if lib.tdk_warp_abi_version() != 1:
     raise ImportError(f'libtdk_hip.so warp ABI version {lib.tdk_warp_abi_version()} != 1')
+  if lib.tdk_raw_abi_version() != 1:
+    raise ImportError(f'libtdk_hip.so raw ABI version {lib.tdk_raw_abi_version()} != 1')
   return lib
 
 

@@ -17,6 +17,7 @@ from .. import tonemap as _tonemap
 from ..bayer import BayerPattern, PackedFormat
 from ..denoise import Wiener
 from ..local_contrast import Bilateral
+from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..white_balance import apply_white_balance
 from .camera_settings import CameraSettings
@@ -39,7 +40,7 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32):
+                 storage_dtype: torch.dtype = torch.float32, raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
         self.device = device
         self.settings = settings
@@ -51,6 +52,12 @@ class ImageProcessor:
         # image storage between the stages: float32 (the reference) or float16 (fp32 arithmetic, half the HBM traffic)
         assert storage_dtype in (torch.float32, torch.float16)
         self.storage_dtype = storage_dtype
+        # sensor correction in front of the demosaic (black / white level, defect pixels, lens shading): replaces decode + white
+        # balance by one kernel that also applies the white balance; None: the reference's chain
+        if raw_correction is not None and (raw_correction.image_size != tuple(image_size) or raw_correction.bayer_pattern != bayer_pattern):
+            raise ValueError(f'raw_correction is for {raw_correction.image_size} {raw_correction.bayer_pattern.name}, '
+                             f'the processor for {tuple(image_size)} {bayer_pattern.name}')
+        self.raw_correction = raw_correction
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -141,6 +148,13 @@ class ImageProcessor:
         return decoded.view(h, w)
 
     def load_image(self, bytes: torch.Tensor) -> torch.Tensor:
+        if self.raw_correction is not None:
+            if bytes.numel() != self.expected_bytes:
+                raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
+                                     f'with {self.padding} padding, got {bytes.numel()} bytes. ')
+            payload = bytes[: bytes.numel() - self.padding] if self.padding > 0 else bytes
+            mosaic = self.raw_correction.process_packed(payload, self.packed_format, white_balance=self.white_balance)
+            return self._demosaic(mosaic).to(self.storage_dtype)   # the white balance is in the mosaic already
         if self.settings.debayer == Debayer.rcd:
             # decode -> white balance -> RCD as one kernel (same result as load_bytes + debayer, two fp32 planes less)
             if bytes.numel() != self.expected_bytes:
@@ -157,6 +171,9 @@ class ImageProcessor:
         assert bayer_image.ndim == 2, f'Bayer image must have 2 dimensions, got {bayer_image.shape}'
         if self.white_balance is not None:
             bayer_image = apply_white_balance(bayer_image, self.white_balance, self.bayer_pattern)
+        return self._demosaic(bayer_image)
+
+    def _demosaic(self, bayer_image: torch.Tensor) -> torch.Tensor:
         mosaic = bayer_image.unsqueeze(-1)
         method = self.settings.debayer
         if method == Debayer.bilinear:
