@@ -35,7 +35,8 @@ CXXFLAGS = ['-O3', '-std=c++17', f'--offload-arch={ARCH}', '-ffp-contract=off', 
 CXXFLAGS += os.environ.get('TDK_EXTRA_FLAGS', '').split()  # experiments: e.g. TDK_EXTRA_FLAGS=-DTDK_WIENER_SHARED_ACC=1
 
 
-HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip.h', 'tdk_hip_ext.h', 'tdk_hip_denoise.h', 'tdk_hip_resample.h', 'tdk_hip_warp.h', 'tdk_hip_raw.h')]
+HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip.h', 'tdk_hip_ext.h', 'tdk_hip_denoise.h', 'tdk_hip_resample.h', 'tdk_hip_warp.h', 'tdk_hip_raw.h',
+                                                       'tdk_hip_sharpen.h')]
 
 
 def _inputs():

@@ -133,12 +133,22 @@ RAW_SIGNATURES = {
   'tdk_raw_prepare_lds_bytes': (c_size_t, [c_int, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_sharpen.h, the unsharp mask (weights: a host pointer to radius + 1 floats)
+SHARPEN_SIGNATURES = {
+  'tdk_sharpen_abi_version': (c_int, []),
+  'tdk_sharpen_weights': (c_int, [c_float, c_void_p, c_void_p]),
+  'tdk_sharpen': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_float, c_float, c_int, c_void_p]),
+  'tdk_sharpen_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+}
+
 TDK_F32, TDK_F16 = 0, 1
 TDK_U8 = 2  # include/tdk_hip_resample.h: taken by tdk_resample and tdk_warp only
 TDK_WARP_DIRECT = 1  # include/tdk_hip_warp.h: flags of tdk_warp
 # include/tdk_hip_raw.h: src_format and defects of tdk_raw_prepare
 TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, TDK_RAW_F32, TDK_RAW_F16 = 0, 1, 2, 3, 4
 TDK_RAW_HOT, TDK_RAW_DEAD = 1, 2
+TDK_SHARPEN_LUMA, TDK_SHARPEN_LIMIT = 1, 2  # include/tdk_hip_sharpen.h: flags of tdk_sharpen
+TDK_SHARPEN_MAX_RADIUS = 12
 
 
 def load() -> C.CDLL:
@@ -148,7 +158,7 @@ def load() -> C.CDLL:
       'torch_darktable has no CPU or pure-PyTorch fallback.'
     )
   lib = C.CDLL(str(_LIB_PATH))
-  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES):
+  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
       fn.restype = restype
@@ -165,6 +175,8 @@ def load() -> C.CDLL:
     raise ImportError(f'libtdk_hip.so warp ABI version {lib.tdk_warp_abi_version()} != 1')
   if lib.tdk_raw_abi_version() != 1:
     raise ImportError(f'libtdk_hip.so raw ABI version {lib.tdk_raw_abi_version()} != 1')
+  if lib.tdk_sharpen_abi_version() != 1:
+    raise ImportError(f'libtdk_hip.so sharpen ABI version {lib.tdk_sharpen_abi_version()} != 1')
   return lib
 
 

@@ -1,7 +1,7 @@
 """packed raw bytes -> uint8 RGB: decode -> [white balance] -> demosaic -> [post-process] ->
-normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> orientation
+normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  `process_resized` / `process_image_set_resized` put the
-antialiased scaler to `final_size` between the tone mapper and the orientation; `process` / `process_image_set` ignore
+antialiased scaler to `final_size` between the tone mapper and the sharpener; `process` / `process_image_set` ignore
 `resize_width`, as the reference does.
 
 Everything between the byte upload and the uint8 result stays on the device: bounds / metrics
@@ -19,6 +19,7 @@ from ..denoise import Wiener
 from ..local_contrast import Bilateral
 from ..rawprepare import RawPrepare
 from ..resample import Resize
+from ..sharpen import Sharpen
 from ..white_balance import apply_white_balance
 from .camera_settings import CameraSettings
 from .config import Debayer, ImageProcessingSettings, ToneMapper
@@ -40,7 +41,7 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, raw_correction: RawPrepare | None = None):
+                 storage_dtype: torch.dtype = torch.float32, sharpen: Sharpen | None = None, raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
         self.device = device
         self.settings = settings
@@ -58,6 +59,10 @@ class ImageProcessor:
             raise ValueError(f'raw_correction is for {raw_correction.image_size} {raw_correction.bayer_pattern.name}, '
                              f'the processor for {tuple(image_size)} {bayer_pattern.name}')
         self.raw_correction = raw_correction
+        # output sharpening of the tone-mapped uint8 frame, after the scaler and before the orientation; None: the reference's chain
+        if sharpen is not None and not isinstance(sharpen, Sharpen):
+            raise TypeError(f'sharpen must be a Sharpen or None, got {type(sharpen).__name__} (raw_correction is the argument after it: pass both by keyword)')
+        self.sharpen = sharpen
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -264,4 +269,6 @@ class ImageProcessor:
         mapped = [self.tonemap(img, self.metrics) for img in rgb]
         if resized and self.resize_workspace is not None:
             mapped = [self.resize_workspace.process(img) for img in mapped]
+        if self.sharpen is not None:
+            mapped = [self.sharpen.process(img) for img in mapped]
         return {name: self.transform(img, name) for name, img in zip(names, mapped)}

@@ -1,0 +1,114 @@
+"""Output sharpening (include/tdk_hip_sharpen.h: tdk_sharpen) -- an unsharp mask with darktable's soft threshold and a halo limit.
+
+The signal (each channel, or the luminance of an RGB frame) is blurred by a separable symmetric kernel with the frame's edge
+replicated; the detail d = s - blur is shrunk towards zero by `threshold`, scaled by `amount` and added back.  With `overshoot`
+the result is held within the 3x3 neighbourhood's minimum and maximum, widened by `overshoot` on both sides, which stops halos at
+strong edges.  `threshold` and `overshoot` are in units of the full range: 1.0 is 255 codes of a uint8 frame.  One kernel launch on
+PyTorch's current stream, no workspace, no synchronisation: capturable in a HIP graph from the first call, and bit-reproducible.
+
+    crisp = Sharpen(device, sigma=1.0, amount=0.5).process(frame)               # (H, W, 1 or 3); float32, float16 or uint8
+    safe = Sharpen(device, sigma=2.0, amount=1.5, threshold=0.01, overshoot=0.02).process(frame)
+"""
+
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+
+from ._native import TDK_F16, TDK_F32, TDK_SHARPEN_LIMIT, TDK_SHARPEN_LUMA, TDK_SHARPEN_MAX_RADIUS, TDK_U8, lib
+from .torch_darktable_extension import _ptr, _require, _stream
+
+MAX_SIZE, MAX_AMOUNT = 65535, 16.0
+_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint8: TDK_U8}
+
+
+class Sharpen:
+    """Unsharp mask on (H, W, C) images of any size.  `luma` sharpens the luminance of C = 3 frames and adds the same detail to
+    all three channels (no colour fringes); it is dropped for C = 1.  `overshoot=None`: no halo limit."""
+
+    TILE = (32, 32)  # (width, height) of one workgroup's output tile (csrc/sharpen.hip: SH_TW, SH_TH)
+
+    def __init__(self, device: torch.device, sigma: float = 1.0, amount: float = 0.5, threshold: float = 0.0, luma: bool = True,
+                 overshoot: float | None = None):
+        sigma = float(sigma)
+        if not 0.25 <= sigma <= 4.0:
+            raise ValueError(f'sigma must lie in [0.25, 4], got {sigma}')
+        buf, radius = (ctypes.c_float * (TDK_SHARPEN_MAX_RADIUS + 1))(), ctypes.c_int(0)
+        if lib.tdk_sharpen_weights(sigma, buf, ctypes.byref(radius)) != 0:
+            raise ValueError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        self._setup(device, tuple(buf[: radius.value + 1]), amount, threshold, luma, overshoot)
+        self.sigma: float | None = sigma
+
+    @staticmethod
+    def from_weights(device: torch.device, weights, amount: float = 0.5, threshold: float = 0.0, luma: bool = True,
+                     overshoot: float | None = None) -> 'Sharpen':
+        """A caller's own symmetric kernel: weights (w0, w1, .. wR), 1 <= R <= 12, finite and >= 0, used as float32.  They are
+        taken as they are; a blur that keeps a flat area flat needs w0 + 2 (w1 + .. + wR) = 1."""
+        self = Sharpen.__new__(Sharpen)
+        weights = tuple(ctypes.c_float(float(w)).value for w in weights)
+        self._setup(device, weights, amount, threshold, luma, overshoot)
+        self.sigma = None
+        return self
+
+    def _setup(self, device, weights, amount, threshold, luma, overshoot) -> None:
+        if device.type != 'cuda':
+            raise ValueError(f'Device must be CUDA, got {device}')
+        if not 2 <= len(weights) <= TDK_SHARPEN_MAX_RADIUS + 1:
+            raise ValueError(f'weights must hold 2..{TDK_SHARPEN_MAX_RADIUS + 1} values (radius 1..{TDK_SHARPEN_MAX_RADIUS}), got {len(weights)}')
+        if not all(math.isfinite(w) and w >= 0.0 for w in weights):
+            raise ValueError(f'weights must be finite and >= 0, got {weights}')
+        if not 0.0 <= float(amount) <= MAX_AMOUNT:
+            raise ValueError(f'amount must lie in [0, {MAX_AMOUNT:g}], got {amount}')
+        if not (math.isfinite(float(threshold)) and float(threshold) >= 0.0):
+            raise ValueError(f'threshold must be finite and >= 0, got {threshold}')
+        if overshoot is not None and not (math.isfinite(float(overshoot)) and float(overshoot) >= 0.0):
+            raise ValueError(f'overshoot must be None or finite and >= 0, got {overshoot}')
+        self._device = device
+        self._weights = weights
+        self._c_weights = (ctypes.c_float * len(weights))(*weights)
+        self.amount, self.threshold, self.luma = float(amount), float(threshold), bool(luma)
+        self.overshoot = None if overshoot is None else float(overshoot)
+
+    @property
+    def weights(self) -> tuple[float, ...]:
+        """The taps w0 .. wR as float32 values."""
+        return self._weights
+
+    @property
+    def radius(self) -> int:
+        return len(self._weights) - 1
+
+    def _flags(self, channels: int) -> int:
+        return (TDK_SHARPEN_LUMA if self.luma and channels == 3 else 0) | (TDK_SHARPEN_LIMIT if self.overshoot is not None else 0)
+
+    def __repr__(self):
+        kernel = f'sigma={self.sigma:g}' if self.sigma is not None else f'weights={self._weights}'
+        return f'Sharpen({kernel}, radius={self.radius}, amount={self.amount:g}, threshold={self.threshold:g}, luma={self.luma}, overshoot={self.overshoot})'
+
+    def lds_bytes(self, channels: int, dtype: torch.dtype) -> int:
+        """LDS one workgroup takes on frames of this kind (0: not a legal call)."""
+        return int(lib.tdk_sharpen_lds_bytes(channels, _TAGS.get(dtype, -1), self.radius, self._flags(channels)))
+
+    def process(self, image: torch.Tensor) -> torch.Tensor:
+        """(H, W, C) -> (H, W, C), C in {1, 3}, float32, float16 or uint8, the same type out."""
+        assert image.dim() == 3, f'image must have 3 dimensions, got {image.shape}'
+        height, width, channels = image.shape
+        if channels not in {1, 3}:
+            raise ValueError(f'image channels must be 1 or 3, got {channels}')
+        if not (1 <= height <= MAX_SIZE and 1 <= width <= MAX_SIZE):
+            raise ValueError(f'image dimensions must be 1..{MAX_SIZE}, got {width}x{height}')
+        _require(image.is_cuda, 'Input must be on CUDA device')
+        _require(image.is_contiguous(), 'Input must be contiguous')
+        _require(image.dtype in _TAGS, 'Input tensor must be float32, float16 or uint8')
+        with torch.cuda.device(image.device):
+            out = torch.empty_like(image)
+            rc = lib.tdk_sharpen(_ptr(image), _ptr(out), width, height, channels, _TAGS[image.dtype], self._c_weights, self.radius, self.amount,
+                                 self.threshold, 0.0 if self.overshoot is None else self.overshoot, self._flags(channels), _stream())
+        if rc != 0:
+            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        return out
+
+
+__all__ = ['Sharpen']
