@@ -253,6 +253,10 @@ int tdk_bilateral_rgb(const void* rgb_in, void* rgb_out, void* workspace, int wi
  * compute_[log_]luminance(rgb_in) if the caller has it (any 4-byte aligned view; 16-byte aligned planes take the vector loads), or NULL. */
 #define TDK_BILATERAL_PREPARED 1u
 #define TDK_BILATERAL_GENERAL_PATH 2u
+/* The Lab form's tile kernel has a flavour compiled for the grid geometry of the default sigmas (2, 0.2), which runs wherever the
+ * planned geometry equals it; TDK_BILATERAL_RUNTIME_GEOMETRY runs the kernel that reads its geometry from its arguments instead
+ * (same bits; the GPU tests compare the two through it, and it is the A/B switch of the measurements). */
+#define TDK_BILATERAL_RUNTIME_GEOMETRY 4u
 int tdk_bilateral_prepare(void* workspace, int width, int height, float sigma_s, float sigma_r, tdk_stream_t stream);
 int tdk_bilateral_ex(const void* lum_in, void* lum_out, void* workspace, int width, int height, float sigma_s, float sigma_r, float detail,
                      int dtype, unsigned flags, tdk_stream_t stream);

@@ -44,6 +44,7 @@ KERNELS = {
     'rcd_stream': ('tdk_rcd', False),
     'rcd_quad': ('tdk_rcd(concurrent)', False),  # register-blocked strips (TDK_RCD_CONCURRENT): same loads and stores
     'rcd_border': ('tdk_rcd(border)', False),
+    'GeomConst': ('tdk_bilateral(tiles,const)', True),  # the constant-geometry flavour of the tile kernel (matched before the general name)
     'bilateral_tile_kernel': ('tdk_bilateral(tiles)', True),
     'bilateral_axis_tables_kernel': ('tdk_bilateral(tables)', False),
     'metrics_kernel': ('tdk_image_metrics', False),

@@ -27,7 +27,7 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 # -ffp-contract=off: no FMA contraction, so + - * / kernels match the strict-fp32 oracle bit for bit.
 # -fno-slp-vectorize: packed fp32 VALU (v_pk_*) issues at half rate on gfx950 and the packing moves
-# cost more than they save (Wiener tile kernel: 4965 -> 4369 VALU instructions, 228 -> 151 VGPRs).
+# cost more than they save (Wiener tile kernel: 4965 -> 4369 VALU instructions).
 CXXFLAGS = ['-O3', '-std=c++17', f'--offload-arch={ARCH}', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-fvisibility=hidden',
             '-Wall', '-Wno-unused-function']
 

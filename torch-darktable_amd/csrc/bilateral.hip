@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "tdk_color.h"
+#include "tdk_bilateral_geometry.h"
 
 #ifdef TDK_BIL_TIMING
 // experiments: clock64() deltas per phase of one workgroup of the tile kernel (profiles/bilateral_phase_exp.py)
@@ -407,6 +408,59 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// ---- the tile's LDS geometry, as the tile kernel sees it (its last template parameter)
+// The layout that follows from a window shape: one set of expressions for plan_tiles and for the constant flavour.
+constexpr int shape_rs(int ncx) { return ncx | 1; }
+constexpr int shape_plane(int ncx, int ncy) { return (shape_rs(ncx) * ncy + 63) / 64 * 64; }
+constexpr int shape_usize(int sz, int ncx, int ncy, int lw, int lh) {
+  const int lt = lw * lh + (ncx + ncy) * (1 + TAB_W), bt = sz * shape_plane(ncx, ncy);  // sample tile + the two table records | blur temp
+  return ((lt > bt ? lt : bt) + 63) / 64 * 64;
+}
+
+// Runtime flavour: every quantity from the kernel arguments, any geometry plan_tiles accepts.
+struct GeomRuntime {
+  static constexpr bool is_const = false;
+  int sz, rs, plane, usize, lw, lh, ncx, ncy, hx, hy;
+  float inv_lw, inv_qw, inv_rs, inv_ncy;
+  __device__ __forceinline__ GeomRuntime(const GridDims& d, const TileLds& L)
+      : sz(d.sz), rs(L.rs), plane(L.plane), usize(L.usize), lw(L.lw), lh(L.lh), ncx(L.ncx), ncy(L.ncy), hx(L.hx), hy(L.hy),
+        inv_lw(L.inv_lw), inv_qw(L.inv_qw), inv_rs(L.inv_rs), inv_ncy(L.inv_ncy) {}
+  __device__ __forceinline__ int div_lw(int i) const { return fast_div(i, inv_lw); }
+  __device__ __forceinline__ int div_qw(int i) const { return fast_div(i, inv_qw); }
+  __device__ __forceinline__ int div_rs(int i) const { return fast_div(i, inv_rs); }
+  __device__ __forceinline__ int div_ncy(int i) const { return fast_div(i, inv_ncy); }
+};
+
+// Constant flavour: the geometry is a function of (width, height, sigma_s, sigma_r) only, the same for every tile, call and
+// frame of a Bilateral object, so for one chosen geometry the compiler may know it: LDS addresses become immediates and
+// shifts, the z loops unroll, the row / column splits are constant divisions, and the splat runs one body without selecting
+// it.  The primary values are the window shape (what plan_tiles finds) and the run lengths of the table records (NMX, NMY:
+// what bilateral_axis_tables_kernel finds; the kernel checks them against its records); launch_tiles runs this flavour only
+// when the planned geometry equals it field by field.
+template <int SZ, int NCX, int NCY, int HX, int HY, int LW, int LH, int NMX, int NMY>
+struct GeomConst {
+  static constexpr bool is_const = true;
+  static constexpr int sz = SZ, ncx = NCX, ncy = NCY, hx = HX, hy = HY, lw = LW, lh = LH, nmx = NMX, nmy = NMY;
+  static constexpr int rs = shape_rs(NCX), plane = shape_plane(NCX, NCY), usize = shape_usize(SZ, NCX, NCY, LW, LH);
+  static_assert(LW % 4 == 0 && HX % 4 == 0 && NMX >= 1 && NMX <= TAB_W && NMY >= 1 && SZ >= 2, "GeomConst: not a shape plan_tiles produces");
+  __device__ __forceinline__ GeomConst(const GridDims&, const TileLds&) {}
+  // the dividends are non-negative and below 2^20 (fast_div): the unsigned constant division gives the same quotient
+  static __device__ __forceinline__ int div_lw(int i) { return (int)((unsigned)i / (unsigned)LW); }
+  static __device__ __forceinline__ int div_qw(int i) { return (int)((unsigned)i / (unsigned)(LW / 4)); }
+  static __device__ __forceinline__ int div_rs(int i) { return (int)((unsigned)i / (unsigned)rs); }
+  static __device__ __forceinline__ int div_ncy(int i) { return (int)((unsigned)i / (unsigned)NCY); }
+  static bool equals(const GridDims& d, const TileLds& L) {
+    return d.sz == sz && L.rs == rs && L.plane == plane && L.usize == usize && L.lw == lw && L.lh == lh && L.ncx == ncx && L.ncy == ncy &&
+           L.hx == hx && L.hy == hy;
+  }
+};
+
+// The geometry of sigma_s = 2, sigma_r = 0.2 (the ImageProcessingSettings defaults, what the pipeline and bench.py run): a 64 x 32
+// tile slices from 33 x 17 cells, + 2 cells of blur halo on either side = 37 x 21; the pixels that splat into them start 7 before
+// the tile (8: whole 4-pixel groups) and end 8 after it; round(1 / 0.2) + 1 = 6 z cells; a cell collects 3 pixels per axis.
+// Nothing here is trusted: launch_tiles compares it with what plan_tiles computes (tests/test_bilateral_geometry.py sweeps it).
+using GeomDefault = GeomConst<6, 37, 21, 8, 7, 80, 47, 3, 3>;
+
 // The tile kernel itself lives in tdk_bilateral_tile.h and is compiled twice: bt_exact (the oracle's bits: MODE 0 / 1 / 2) and bt_fast
 // (contraction + factored slice for the Lab hand-over chain, MODE 3).
 #define TDK_BT_FAST 0
@@ -426,7 +480,20 @@ constexpr size_t FUSED_LDS_LIMIT = 80 * 1024;  // two workgroups per CU
 
 // Decide whether the tile kernel applies and size its LDS.  Returns false -> four-kernel path.
 // sigma_s <= 4: the pixels with a positive weight on one cell lie within sigma_s of it on either side, at most 7 <= TAB_W.
-static bool plan_tiles(int width, int height, const GridDims& d, float sigma_s, float sigma_r, float detail, TileLds* L, size_t* lds_bytes) {
+// every tile along one axis: its cells fit in nc, and the pixels that splat into them lie in the window of lp pixels that starts
+// `halo` before the tile
+static bool shape_contains(int size_px, int tile, int size_cells, float sigma_s, int nc, int halo, int lp) {
+  for (int p0 = 0; p0 < size_px; p0 += tile) {
+    const AxisTile t = axis_tile(p0, tile, size_px, size_cells, sigma_s);
+    const int lo = win_lo(p0, halo);
+    if (t.nc > nc || t.p_lo < lo || t.p_lo + t.np > lo + win_np(lo, lp, size_px)) return false;
+  }
+  return true;
+}
+
+// minimal (optional, 6 ints): ncx, ncy, hx, hy, lw, lh as this image alone needs them, before the constant geometry's shape is considered
+static bool plan_tiles(int width, int height, const GridDims& d, float sigma_s, float sigma_r, float detail, TileLds* L, size_t* lds_bytes,
+                       int* minimal = nullptr) {
   if (!(sigma_s >= 1.0f && sigma_s <= 4.0f)) return false;
   // no pixel may be clamped onto the last column / row (those columns collect far-away pixels)
   if ((float)(width - 1) / sigma_s > (float)(d.sx - 1) || (float)(height - 1) / sigma_s > (float)(d.sy - 1)) return false;
@@ -454,10 +521,19 @@ static bool plan_tiles(int width, int height, const GridDims& d, float sigma_s, 
     const int n = t.p_lo + t.np - win_lo(y0, hy);
     lh = n > lh ? n : lh;
   }
-  L->rs = ncx | 1;
-  L->plane = (int)tdk_align_up((size_t)L->rs * ncy, 64);
-  const int lt = lw * lh + (ncx + ncy) * (1 + TAB_W), bt = d.sz * L->plane;  // sample tile + the two table records | blur temp
-  L->usize = (int)tdk_align_up((size_t)(lt > bt ? lt : bt), 64);
+  if (minimal) { minimal[0] = ncx; minimal[1] = ncy; minimal[2] = hx; minimal[3] = hy; minimal[4] = lw; minimal[5] = lh; }
+  // An image of only a few tiles needs less than the shape of an image of many (its windows end at the image's edge).  Where
+  // the constant geometry's shape contains what every tile column and row asks for, plan that shape: a window that reaches
+  // beyond the image is clipped per tile anyway (npx / npy, as in the last tile column and row of every image), the values
+  // computed are the same, and the image runs the constant-geometry kernel.
+  using C = GeomDefault;
+  if (d.sz == C::sz && ncx <= C::ncx && ncy <= C::ncy && shape_contains(width, FTW, d.sx, sigma_s, C::ncx, C::hx, C::lw) &&
+      shape_contains(height, FTH, d.sy, sigma_s, C::ncy, C::hy, C::lh)) {
+    ncx = C::ncx; ncy = C::ncy; hx = C::hx; hy = C::hy; lw = C::lw; lh = C::lh;
+  }
+  L->rs = shape_rs(ncx);
+  L->plane = shape_plane(ncx, ncy);
+  L->usize = shape_usize(d.sz, ncx, ncy, lw, lh);
   L->lw = lw; L->lh = lh;
   L->ncx = ncx; L->ncy = ncy;
   L->hx = hx; L->hy = hy;
@@ -487,7 +563,8 @@ static int build_tables(int* tab, int width, int height, const GridDims& d, floa
 
 template <typename TL, typename T, int MODE>
 int launch_tiles(const TL* lum, const T* rgb, T* out, int* tab, int width, int height, const GridDims& d, float sigma_s, float sigma_r, float detail,
-                 const TileLds& L, size_t lds_bytes, bool vec, bool prepared, hipStream_t s) {
+                 const TileLds& L, size_t lds_bytes, bool vec, unsigned flags, hipStream_t s) {
+  const bool prepared = (flags & TDK_BILATERAL_PREPARED) != 0;
   const int tiles_x = tdk_div_up(width, FTW), tiles_y = tdk_div_up(height, FTH), ntiles = tiles_x * tiles_y;
   const dim3 grid(8 * tdk_div_up(ntiles, 8));
 #ifdef TDK_EXPERIMENTS
@@ -503,7 +580,15 @@ int launch_tiles(const TL* lum, const T* rgb, T* out, int* tab, int width, int h
     TDK_LAUNCH("tdk_bilateral(tiles)", (NS::bilateral_tile_kernel<TL, T, MODE, VECV>), grid, dim3(FNT), lds_bytes, s, lum, rgb, out, tab, width, height, d, \
                sigma_r, tiles_x, ntiles, L);                                                                                                      \
   } while (0)
-  if constexpr (MODE == 3) { if (vec) TDK_BT(bt_fast, 4); else TDK_BT(bt_fast, 1); }
+  if constexpr (MODE == 3) {
+    // the constant-geometry flavour where the planned geometry is exactly its own (other sigmas, VEC 1, MODE 0 - 2: as planned)
+    if (vec && !(flags & TDK_BILATERAL_RUNTIME_GEOMETRY) && GeomDefault::equals(d, L)) {
+      TDK_MAX_LDS_ONCE((bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault>), "tdk_bilateral(hipFuncSetAttribute)");
+      TDK_LAUNCH("tdk_bilateral(tiles,const)", (bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault>), grid, dim3(FNT), lds_bytes, s, lum, rgb, out, tab,
+                 width, height, d, sigma_r, tiles_x, ntiles, L);
+    } else if (vec) TDK_BT(bt_fast, 4);
+    else TDK_BT(bt_fast, 1);
+  }
   else { if (vec) TDK_BT(bt_exact, 4); else TDK_BT(bt_exact, 1); }
 #undef TDK_BT
   return TDK_OK;
@@ -553,7 +638,7 @@ int launch(const void* lum_in, void* lum_out, void* workspace, int width, int he
   if (tiles) {
     const bool vec = (width % 4) == 0 && tdk_aligned(lum_in, 16) && tdk_aligned(lum_out, 16);
     return launch_tiles<T, T, 0>(in, nullptr, reinterpret_cast<T*>(lum_out), tab, width, height, d, sigma_s, sigma_r, detail, L, lds_bytes, vec,
-                                 (flags & TDK_BILATERAL_PREPARED) != 0, s);
+                                 flags, s);
   }
   const int rc = build_grid<T>(in, grid, tmp, width, height, d, sigma_s, sigma_r, s);
   if (rc != TDK_OK) return rc;
@@ -582,9 +667,8 @@ int launch_rgb(const void* rgb_in, void* rgb_out, void* workspace, int width, in
   TileLds L;
   size_t lds_bytes = 0;
   if (!(flags & TDK_BILATERAL_GENERAL_PATH) && plan_tiles(width, height, d, sigma_s, sigma_r, detail, &L, &lds_bytes)) {
-    const bool prepared = (flags & TDK_BILATERAL_PREPARED) != 0;
-    if (log_mode) return launch_tiles<float, T, 2>(plane, reinterpret_cast<const T*>(rgb_in), reinterpret_cast<T*>(rgb_out), tab, width, height, d, sigma_s, sigma_r, detail, L, lds_bytes, vec, prepared, s);
-    return launch_tiles<float, T, 1>(plane, reinterpret_cast<const T*>(rgb_in), reinterpret_cast<T*>(rgb_out), tab, width, height, d, sigma_s, sigma_r, detail, L, lds_bytes, vec, prepared, s);
+    if (log_mode) return launch_tiles<float, T, 2>(plane, reinterpret_cast<const T*>(rgb_in), reinterpret_cast<T*>(rgb_out), tab, width, height, d, sigma_s, sigma_r, detail, L, lds_bytes, vec, flags, s);
+    return launch_tiles<float, T, 1>(plane, reinterpret_cast<const T*>(rgb_in), reinterpret_cast<T*>(rgb_out), tab, width, height, d, sigma_s, sigma_r, detail, L, lds_bytes, vec, flags, s);
   }
   rc = build_grid<float>(plane, grid, tmp, width, height, d, sigma_s, sigma_r, s);
   if (rc != TDK_OK) return rc;
@@ -613,7 +697,7 @@ int launch_lab(const float* lum, const float* ab, void* rgb_out, void* workspace
   if (!(flags & TDK_BILATERAL_GENERAL_PATH) && plan_tiles(width, height, d, sigma_s, sigma_r, detail, &L, &lds_bytes)) {
     const bool vec = (width % 4) == 0 && tdk_aligned(rgb_out, 16) && tdk_aligned(lum, 16) && tdk_aligned(ab, 16);
     return launch_tiles<float, T, 3>(lum, reinterpret_cast<const T*>(ab), reinterpret_cast<T*>(rgb_out), tab, width, height, d, sigma_s, sigma_r, detail, L, lds_bytes,
-                                     vec, (flags & TDK_BILATERAL_PREPARED) != 0, s);
+                                     vec, flags, s);
   }
   const int rc = build_grid<float>(lum, grid, tmp, width, height, d, sigma_s, sigma_r, s);
   if (rc != TDK_OK) return rc;
@@ -629,8 +713,25 @@ TDK_EXPORT int tdk_bilateral_lab(const float* lum_in, const float* ab_in, void* 
   TDK_REQUIRE(lum_in && ab_in && rgb_out && workspace, "tdk_bilateral_lab: null pointer");
   TDK_REQUIRE(width > 0 && height > 0, "Invalid dimensions");
   TDK_REQUIRE(sigma_s > 0.0f && sigma_r > 0.0f, "tdk_bilateral_lab: sigmas must be positive");
-  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH)) == 0, "tdk_bilateral_lab: unknown flags 0x%x", flags);
+  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH | TDK_BILATERAL_RUNTIME_GEOMETRY)) == 0, "tdk_bilateral_lab: unknown flags 0x%x", flags);
   TDK_DISPATCH_DTYPE(out_dtype, T, return launch_lab<T>(lum_in, ab_in, rgb_out, workspace, width, height, sigma_s, sigma_r, detail, flags, tdk_stream(stream)));
+  return TDK_OK;
+}
+
+// Host only: the tile kernel's geometry for an image and the dispatch decision of launch_tiles, without a launch.
+TDK_EXPORT int tdk_bilateral_tile_geometry(int width, int height, float sigma_s, float sigma_r, int planned[TDK_BILATERAL_GEOMETRY_WORDS],
+                                           int minimal[6], int constant[TDK_BILATERAL_GEOMETRY_WORDS]) {
+  TDK_REQUIRE(width > 0 && height > 0 && sigma_s > 0.0f && sigma_r > 0.0f && planned && minimal && constant, "tdk_bilateral_tile_geometry: invalid arguments");
+  using C = GeomDefault;
+  const int cs[TDK_BILATERAL_GEOMETRY_WORDS] = {1, 1, C::sz, C::rs, C::plane, C::usize, C::lw, C::lh, C::ncx, C::ncy, C::hx, C::hy};
+  for (int i = 0; i < TDK_BILATERAL_GEOMETRY_WORDS; i++) { constant[i] = cs[i]; planned[i] = 0; }
+  for (int i = 0; i < 6; i++) minimal[i] = 0;
+  const GridDims d = compute_grid_size(width, height, sigma_s, sigma_r);
+  TileLds L;
+  size_t lds_bytes = 0;
+  if (!plan_tiles(width, height, d, sigma_s, sigma_r, 0.0f, &L, &lds_bytes, minimal)) return TDK_OK;  // the four-kernel path
+  const int ps[TDK_BILATERAL_GEOMETRY_WORDS] = {1, C::equals(d, L) ? 1 : 0, d.sz, L.rs, L.plane, L.usize, L.lw, L.lh, L.ncx, L.ncy, L.hx, L.hy};
+  for (int i = 0; i < TDK_BILATERAL_GEOMETRY_WORDS; i++) planned[i] = ps[i];
   return TDK_OK;
 }
 
@@ -669,7 +770,7 @@ TDK_EXPORT int tdk_bilateral_ex(const void* lum_in, void* lum_out, void* workspa
   TDK_REQUIRE(lum_in && lum_out && workspace, "tdk_bilateral: null pointer");
   TDK_REQUIRE(width > 0 && height > 0, "Invalid dimensions");
   TDK_REQUIRE(sigma_s > 0.0f && sigma_r > 0.0f, "tdk_bilateral: sigmas must be positive");
-  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH)) == 0, "tdk_bilateral: unknown flags 0x%x", flags);
+  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH | TDK_BILATERAL_RUNTIME_GEOMETRY)) == 0, "tdk_bilateral: unknown flags 0x%x", flags);
   TDK_DISPATCH_DTYPE(dtype, T, return launch<T>(lum_in, lum_out, workspace, width, height, sigma_s, sigma_r, detail, flags, tdk_stream(stream)));
   return TDK_OK;
 }
@@ -685,7 +786,7 @@ TDK_EXPORT int tdk_bilateral_rgb_ex(const void* rgb_in, const float* lum_in, voi
   TDK_REQUIRE(width > 0 && height > 0, "Invalid dimensions");
   TDK_REQUIRE(sigma_s > 0.0f && sigma_r > 0.0f, "tdk_bilateral_rgb: sigmas must be positive");
   TDK_REQUIRE(!log_mode || eps > 0.0f, "Epsilon must be positive");
-  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH)) == 0, "tdk_bilateral_rgb: unknown flags 0x%x", flags);
+  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH | TDK_BILATERAL_RUNTIME_GEOMETRY)) == 0, "tdk_bilateral_rgb: unknown flags 0x%x", flags);
   TDK_DISPATCH_DTYPE(dtype, T, return launch_rgb<T>(rgb_in, rgb_out, workspace, width, height, sigma_s, sigma_r, detail, log_mode, eps, dtype, flags, tdk_stream(stream), lum_in));
   return TDK_OK;
 }

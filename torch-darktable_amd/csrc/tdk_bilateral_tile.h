@@ -6,7 +6,10 @@
 //            the colour operators' tolerance anyway: sample coordinate L * (1 / sigma_r) instead of the exact quotient, splat
 //            contributions and blurs as fused multiply-adds, the trilinear slice factored into seven lerps (14 instructions
 //            instead of the 31 of the eight-term sum of triple products).  Differences ~1e-6 of the lightness.
-// Shares with bilateral.hip: GridDims, TileLds, AxisTile, tab_rec, win_lo / win_np, fast_div, lds_barrier, FTW / FTH / FNT, TAB_*.
+// Shares with bilateral.hip: GridDims, TileLds, AxisTile, tab_rec, win_lo / win_np, fast_div, lds_barrier, FTW / FTH / FNT, TAB_*,
+// and the two geometry flavours GeomRuntime / GeomConst (the kernel's last template parameter): the LDS grid's shape either read from
+// the kernel arguments or known to the compiler.  Only integer addressing and control flow differ between the two; every
+// floating-point expression is the same, in the same order, so both give the same bits.
 
 // The NX candidate pixels per row of one cell column, nmy rows: raster order, each pixel adds its two z
 // contributions to the column (read both cells, then write both: one LDS round trip per pixel).
@@ -80,7 +83,7 @@ __device__ __forceinline__ void sample_gz(const float (&v)[N], float (&g)[N], fl
 // MODE 0: luminance plane in (TL == T) -> filtered plane out; 1 / 2: fp32 plane + RGB in -> RGB out (linear / log);
 // 3: fp32 plane + the pixels' Lab chroma (a, b: two floats per pixel, passed through the `rgb` pointer) in -> RGB out: the Lab
 // hand-over chain (color.hip: lum_lab_extract) -- modify_luminance without its RGB -> Lab half
-template <typename TL, typename T, int MODE, int VEC>
+template <typename TL, typename T, int MODE, int VEC, typename G = GeomRuntime>
 #ifndef TDK_BIL_WPE
 #define TDK_BIL_WPE 8  // waves per SIMD the register budget is set for (experiments: co-residency with other frames' kernels)
 #endif
@@ -88,15 +91,16 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
     const TL* __restrict__ lum, const T* __restrict__ rgb, T* __restrict__ out, const int* __restrict__ tab, int width, int height, GridDims d,
     float sigma_r, int tiles_x, int ntiles, TileLds L) {
   extern __shared__ float smem[];
+  const G geo(d, L);
 #ifdef TDK_BIL_TIMING
   unsigned long long bil_t0 = clock64();
 #endif
   float* A = smem;                      // [sz][plane] grid, cell (lx, ly) at ly * RS + lx
-  float* U = A + d.sz * L.plane;        // z sample coordinate of every pixel of the sample window (lh rows of lw), then blur temp
-  float* gxs = U + L.usize;             // x sample coordinate of pixel column px_lo + i
-  float* gys = gxs + L.lw;
-  int* TX = reinterpret_cast<int*>(U + L.lw * L.lh);  // (tail of U, dead before the blur) x record: start[ncx] then weights[ncx][TAB_W]
-  int* TY = TX + L.ncx * (1 + TAB_W);
+  float* U = A + geo.sz * geo.plane;        // z sample coordinate of every pixel of the sample window (lh rows of lw), then blur temp
+  float* gxs = U + geo.usize;             // x sample coordinate of pixel column px_lo + i
+  float* gys = gxs + geo.lw;
+  int* TX = reinterpret_cast<int*>(U + geo.lw * geo.lh);  // (tail of U, dead before the blur) x record: start[ncx] then weights[ncx][TAB_W]
+  int* TY = TX + geo.ncx * (1 + TAB_W);
 
   // consecutive workgroup ids go round-robin over the 8 XCDs: give each XCD a contiguous run of tiles
   const int chunk = gridDim.x >> 3;
@@ -104,14 +108,14 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
   if (tile >= ntiles) return;
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   const int x0 = txi * FTW, y0 = tyi * FTH;
-  const int recx = tab_rec(L.lw, L.ncx), recy = tab_rec(L.lh, L.ncy);
+  const int recx = tab_rec(geo.lw, geo.ncx), recy = tab_rec(geo.lh, geo.ncy);
   const int* rx = tab + txi * recx;
   const int* ry = tab + tiles_x * recx + tyi * recy;
-  const int px_lo = win_lo(x0, L.hx), py_lo = win_lo(y0, L.hy);
-  const int npx = win_np(px_lo, L.lw, width), npy = win_np(py_lo, L.lh, height);
+  const int px_lo = win_lo(x0, geo.hx), py_lo = win_lo(y0, geo.hy);
+  const int npx = win_np(px_lo, geo.lw, width), npy = win_np(py_lo, geo.lh, height);
   const int tid = threadIdx.x;
-  const int PS = L.plane, RS = L.rs, LWS = L.lw;
-  const float ztop = (float)(d.sz - 1), rc_r = L.rc_r;
+  const int PS = geo.plane, RS = geo.rs, LWS = geo.lw;
+  const float ztop = (float)(geo.sz - 1), rc_r = L.rc_r;
 
   // ---- set-up: the tile's luminance samples and its two table records into LDS.  All global loads are issued before
   // the first one is waited for; their addresses need nothing but the kernel arguments.
@@ -122,15 +126,15 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
       if (tid + FNT < n) dst[tid + FNT] = from[tid + FNT];
     };
     auto copy_records = [&]() {
-      copy2(reinterpret_cast<int*>(gxs), rx + TAB_HDR, L.lw);
-      copy2(reinterpret_cast<int*>(gys), ry + TAB_HDR, L.lh);
-      copy2(TX, rx + TAB_HDR + L.lw, L.ncx * (1 + TAB_W));
-      copy2(TY, ry + TAB_HDR + L.lh, L.ncy * (1 + TAB_W));
+      copy2(reinterpret_cast<int*>(gxs), rx + TAB_HDR, geo.lw);
+      copy2(reinterpret_cast<int*>(gys), ry + TAB_HDR, geo.lh);
+      copy2(TX, rx + TAB_HDR + geo.lw, geo.ncx * (1 + TAB_W));
+      copy2(TY, ry + TAB_HDR + geo.lh, geo.ncy * (1 + TAB_W));
     };
     const TL* src = lum + (size_t)py_lo * width + px_lo;
     if constexpr (VEC == 4) {
       // 4 samples per load: the window starts on a multiple of 4 pixels, the rows are 16-B aligned (host-checked)
-      const int qw = L.lw >> 2, total = qw * npy;
+      const int qw = geo.lw >> 2, total = qw * npy;
       constexpr int NB = 2;
       for (int base = tid; base - tid < total; base += NB * FNT) {  // uniform trip count: every thread helps copy the records
         float v[NB][4];
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
 #pragma unroll
         for (int k = 0; k < NB; k++) {
           const int q = base + k * FNT;
-          const int r = fast_div(q, L.inv_qw), c = (q - r * qw) * 4;
+          const int r = geo.div_qw(q), c = (q - r * qw) * 4;
           at[k] = (q < total && c < npx) ? r * LWS + c : -1;
           if (at[k] >= 0) s4_io<TL>::load(src + (size_t)r * width + c, 0, v[k]);
         }
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
 #pragma unroll
         for (int k = 0; k < NB; k++) {
           const int i = base + k * FNT;
-          const int r = fast_div(i, L.inv_lw), c = i - r * LWS;
+          const int r = geo.div_lw(i), c = i - r * LWS;
           on[k] = i < total && c < npx;
           v[k] = on[k] ? ld(src, (size_t)r * width + c) : 0.0f;
         }
@@ -186,27 +190,38 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
   const float contrib = L.contrib;
   {
     const int ncol = RS * ay.nc;
-    const float* WX = reinterpret_cast<const float*>(TX + L.ncx);
-    const float* WY = reinterpret_cast<const float*>(TY + L.ncy);
+    const float* WX = reinterpret_cast<const float*>(TX + geo.ncx);
+    const float* WY = reinterpret_cast<const float*>(TY + geo.ncy);
     for (int c = tid; c < ncol; c += FNT) {
-      const int ly = fast_div(c, L.inv_rs), lx = c - ly * RS;
+      const int ly = geo.div_rs(c), lx = c - ly * RS;
       if (lx >= ax.nc) continue;  // padding column of the odd row stride
       const int xa = TX[lx], ya = TY[ly];
       float* acc = A + c;
-      for (int z = 0; z < d.sz; z++) acc[z * PS] = 0.0f;
+      for (int z = 0; z < geo.sz; z++) acc[z * PS] = 0.0f;
       if (xa < 0 || ya < 0) continue;  // cell outside the grid: stays zero
       const float* urow = U + ya * LWS + xa;
       const float* wxp = WX + lx;
       const float* wyp = WY + ly;
-      switch (nmx) {
-        case 1: splat_column<1>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        case 2: splat_column<2>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        case 3: splat_column<3>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        case 4: splat_column<4>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        case 5: splat_column<5>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        case 6: splat_column<6>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        case 7: splat_column<7>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
-        default: splat_column<8>(acc, urow, wxp, L.ncx, wyp, L.ncy, nmy, LWS, PS, d.sz, contrib); break;
+      // the records' run lengths are known for the constant geometry (3 x 3 pixels per cell at sigma_s = 2); a record that
+      // disagrees (it cannot in an image of more than a few pixels) takes the general selection below
+      bool splat_done = false;
+      if constexpr (G::is_const) {
+        if (nmx == G::nmx && nmy == G::nmy) {
+          splat_column<G::nmx>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, G::nmy, LWS, PS, geo.sz, contrib);
+          splat_done = true;
+        }
+      }
+      if (!splat_done) {
+        switch (nmx) {
+          case 1: splat_column<1>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          case 2: splat_column<2>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          case 3: splat_column<3>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          case 4: splat_column<4>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          case 5: splat_column<5>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          case 6: splat_column<6>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          case 7: splat_column<7>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+          default: splat_column<8>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, nmy, LWS, PS, geo.sz, contrib); break;
+        }
       }
     }
   }
@@ -219,8 +234,8 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
   const float w0 = 6.0f / 16.0f, w1 = 4.0f / 16.0f, w2 = 1.0f / 16.0f;
   {
     constexpr int CH = 13;
-    for (int row = tid; row < d.sz * L.ncy; row += FNT) {
-      const int z = fast_div(row, L.inv_ncy), ly = row - z * L.ncy;
+    for (int row = tid; row < geo.sz * geo.ncy; row += FNT) {
+      const int z = geo.div_ncy(row), ly = row - z * geo.ncy;
       if (ly >= ay.nc) continue;
       const float* p = A + z * PS + ly * RS;
       float* q = U + z * PS + ly * RS;
@@ -242,8 +257,8 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
   // ---- blur y: U -> A, one thread per (z, column)
   {
     constexpr int CH = 11;
-    for (int cc = tid; cc < d.sz * RS; cc += FNT) {
-      const int z = fast_div(cc, L.inv_rs), lx = cc - z * RS;
+    for (int cc = tid; cc < geo.sz * RS; cc += FNT) {
+      const int z = geo.div_rs(cc), lx = cc - z * RS;
       if (lx >= ax.nc) continue;
       const float* p = U + z * PS + lx;
       float* q = A + z * PS + lx;
@@ -268,19 +283,19 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
     constexpr int ZR = 8;
     for (int c = tid; c < RS * ay.nc; c += FNT) {
       float* p = A + c;
-      if (d.sz <= ZR) {
+      if (geo.sz <= ZR) {
         float v[ZR + 4];
         v[0] = v[1] = 0.0f;
 #pragma unroll
-        for (int z = 0; z < ZR + 2; z++) v[z + 2] = (z < d.sz) ? p[z * PS] : 0.0f;
+        for (int z = 0; z < ZR + 2; z++) v[z + 2] = (z < geo.sz) ? p[z * PS] : 0.0f;
 #pragma unroll
         for (int z = 0; z < ZR; z++)
-          if (z < d.sz) p[z * PS] = v1 * (v[z + 3] - v[z + 1]) + v2 * (v[z + 4] - v[z]);
+          if (z < geo.sz) p[z * PS] = v1 * (v[z + 3] - v[z + 1]) + v2 * (v[z + 4] - v[z]);
       } else {
         float m2 = 0.0f, m1 = 0.0f, c0 = p[0];
-        float p1 = (d.sz > 1) ? p[PS] : 0.0f;
-        for (int z = 0; z < d.sz; z++) {
-          const float p2 = (z + 2 < d.sz) ? p[(z + 2) * PS] : 0.0f;
+        float p1 = (geo.sz > 1) ? p[PS] : 0.0f;
+        for (int z = 0; z < geo.sz; z++) {
+          const float p2 = (z + 2 < geo.sz) ? p[(z + 2) * PS] : 0.0f;
           p[z * PS] = v1 * (p1 - m1) + v2 * (p2 - m2);
           m2 = m1; m1 = c0; c0 = p1; p1 = p2;
         }
@@ -325,7 +340,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
       const int ix = min((int)gx, d.sx - 2);
       const float bx = gx - (float)ix, axw = 1.0f - bx;
       const float gz = gzv[k];
-      const int iz = min((int)gz, d.sz - 2);
+      const int iz = min((int)gz, geo.sz - 2);
       const float bz = gz - (float)iz, azw = 1.0f - bz;
       const int oy = RS, oz = PS;
       const float* gp = grow + iz * PS + ix;

@@ -54,18 +54,20 @@ class BayerPattern(enum.IntEnum):
 # Two ops have a second kernel path that gives the same bits (RCD: 64 x 64 LDS tiles instead of the column strips; Bilateral:
 # the four-kernel path instead of the LDS tile kernel).  The library selects per call (the `flags` of tdk_rcd_ex /
 # tdk_bilateral_ex); this thread-local context is how the GPU tests ask for the other path.  Nothing is process-global.
-TDK_RCD_TILE_KERNEL, TDK_RCD_CONCURRENT, TDK_RCD_EXACT, TDK_BILATERAL_PREPARED, TDK_BILATERAL_GENERAL_PATH = 1, 2, 4, 1, 2
+TDK_RCD_TILE_KERNEL, TDK_RCD_CONCURRENT, TDK_RCD_EXACT, TDK_BILATERAL_PREPARED, TDK_BILATERAL_GENERAL_PATH, TDK_BILATERAL_RUNTIME_GEOMETRY = 1, 2, 4, 1, 2, 4
 _verify = threading.local()
 
 
 @contextlib.contextmanager
-def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False, rcd_exact: bool = False):
+def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False, rcd_exact: bool = False, bilateral_runtime_geometry: bool = False):
   """Inside the context (this thread only) RCD.process takes the tile kernel and / or Bilateral the four-kernel path.
   rcd_exact: a float16 result of RCD.process is the exact flavour's result rounded once (TDK_RCD_EXACT) instead of the default
-  approximate arithmetic of the column strips (include/tdk_hip.h); float32 results are always exact."""
+  approximate arithmetic of the column strips (include/tdk_hip.h); float32 results are always exact.
+  bilateral_runtime_geometry: Bilateral.process_lab runs the tile kernel that reads its grid geometry from its arguments where the
+  one compiled for the default sigmas' geometry would run (TDK_BILATERAL_RUNTIME_GEOMETRY: the same bits)."""
   old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0))
   _verify.rcd = (TDK_RCD_TILE_KERNEL if rcd_tiles else 0) | (TDK_RCD_EXACT if rcd_exact else 0)
-  _verify.bil = TDK_BILATERAL_GENERAL_PATH if bilateral_general else 0
+  _verify.bil = (TDK_BILATERAL_GENERAL_PATH if bilateral_general else 0) | (TDK_BILATERAL_RUNTIME_GEOMETRY if bilateral_runtime_geometry else 0)
   try:
     yield
   finally:
