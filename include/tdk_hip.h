@@ -257,6 +257,11 @@ int tdk_bilateral_rgb(const void* rgb_in, void* rgb_out, void* workspace, int wi
  * planned geometry equals it; TDK_BILATERAL_RUNTIME_GEOMETRY runs the kernel that reads its geometry from its arguments instead
  * (same bits; the GPU tests compare the two through it, and it is the A/B switch of the measurements). */
 #define TDK_BILATERAL_RUNTIME_GEOMETRY 4u
+/* The constant-geometry flavour holds two bodies of the same phases: a general one, and an interior one that it takes for every
+ * tile whose table records and sample window do not touch the frame's edge (no guard against the edge can bind there, so each is
+ * a compile-time constant).  TDK_BILATERAL_GENERAL_BODY (tdk_bilateral_lab only) runs the flavour with the general body alone
+ * (same bits; the GPU tests compare the two through it). */
+#define TDK_BILATERAL_GENERAL_BODY 8u
 int tdk_bilateral_prepare(void* workspace, int width, int height, float sigma_s, float sigma_r, tdk_stream_t stream);
 int tdk_bilateral_ex(const void* lum_in, void* lum_out, void* workspace, int width, int height, float sigma_s, float sigma_r, float detail,
                      int dtype, unsigned flags, tdk_stream_t stream);

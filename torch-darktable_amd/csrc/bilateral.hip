@@ -24,6 +24,8 @@
 //  formulas (x + 0 == x); and the gather sums in raster order, so the whole op is bit-identical to the oracle.
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "tdk_color.h"
 #include "tdk_bilateral_geometry.h"
 
@@ -91,8 +93,9 @@ __device__ __forceinline__ Sample make_sample(int x, int y, float L, GridDims d,
 // float sums come out in the same order as a sequential raster-order splat, i.e. bit-identical
 // to the oracle and identical run to run (the reference's atomic order is not).
 // A pixel contributes to column cx when its base cell is cx (weight 1 - f) or cx - 1 (weight f).
-__device__ __forceinline__ float axis_weight(int p, float sigma_s, int size, int cell) {
-  const float g = clampf((float)p / sigma_s, 0.0f, (float)(size - 1));
+// (host too: tile_counts restates the run lengths of the axis tables; plain IEEE float ops, so both sides agree exactly)
+__host__ __device__ __forceinline__ float axis_weight(int p, float sigma_s, int size, int cell) {
+  const float g = fminf(fmaxf((float)p / sigma_s, 0.0f), (float)(size - 1));  // clampf
   const int ib = min((int)g, size - 2);
   const float f = g - (float)ib;
   return (ib == cell) ? (1.0f - f) : ((ib == cell - 1) ? f : -1.0f);  // -1: no contribution
@@ -344,6 +347,27 @@ __host__ __device__ inline int win_np(int lo, int lp, int size_px) { return lo +
 // (relative to the window start; -1: cell outside the grid), then TAB_W weights per cell, k-major
 __host__ __device__ inline int tab_rec(int lp, int nc) { return TAB_HDR + lp + nc * (1 + TAB_W); }
 
+// The run of pixels of the window [p_lo, p_lo + np) with a positive weight on `cell`: first and last pixel (k0 = k1 = -1: none) and
+// the first candidate a.  Shared by bilateral_axis_tables_kernel and the host's restatement of its records (record_header).
+__host__ __device__ inline void cell_run(int cell, int p_lo, int np, float sigma_s, int size_cells, int* a_out, int* k0_out, int* k1_out) {
+  const int a0 = (int)floorf(sigma_s * (float)(cell - 1)) - 1, b0 = (int)ceilf(sigma_s * (float)(cell + 1)) + 1;
+  const int a = a0 > p_lo ? a0 : p_lo, b = b0 < p_lo + np - 1 ? b0 : p_lo + np - 1;
+  int k0 = -1, k1 = -1;
+  for (int p = a; p <= b; p++)
+    if (axis_weight(p, sigma_s, size_cells, cell) > 0.0f) { if (k0 < 0) k0 = p; k1 = p; }
+  *a_out = a; *k0_out = k0; *k1_out = k1;
+}
+
+// One axis of the interior rule (tdk_bilateral_tile.h: tile_is_interior), on a record's header values c_lo, nc, nmax and the tile's
+// first pixel p0, for the constant geometry's NC cells, run length NM, halo HALO and window of LP pixels: the record keeps the
+// constant number of cells and all of them lie inside the grid (then no record start is negative, and the sliced cells stay below
+// the last one: ix <= size_cells - 4), its run length is the constant one, and the sample window starts its whole halo before the
+// tile and ends inside the frame (then so does the tile).  The ONE statement of the rule: the kernel evaluates it on the records
+// it reads, tdk_bilateral_tile_interior on the header values the host computes (record_header).
+__host__ __device__ inline bool axis_header_is_interior(int c_lo, int nc, int nmax, int p0, int size_cells, int size_px, int NC, int NM, int HALO, int LP) {
+  return c_lo >= 0 && nc == NC && c_lo + NC <= size_cells && nmax == NM && p0 >= HALO && p0 - HALO + LP <= size_px;
+}
+
 // One 64-thread workgroup per tile column, then per tile row.  For a cell, the pixels with a positive weight
 // (axis_weight above) are consecutive; the record keeps the first one and nmax weights, nmax = the longest run of
 // the record, shorter runs padded with zero weights (a zero weight adds +0 to a non-negative sum: no bit changes)
@@ -369,11 +393,8 @@ __global__ __launch_bounds__(64) void bilateral_axis_tables_kernel(int* __restri
     const int cell = t.c_lo + l;
     int first = -1;
     if (cell >= 0 && cell < size_cells) {
-      const int a = max(p_lo, (int)floorf(sigma_s * (float)(cell - 1)) - 1);
-      const int b = min(p_lo + np - 1, (int)ceilf(sigma_s * (float)(cell + 1)) + 1);
-      int k0 = -1, k1 = -1;
-      for (int p = a; p <= b; p++)
-        if (axis_weight(p, sigma_s, size_cells, cell) > 0.0f) { if (k0 < 0) k0 = p; k1 = p; }
+      int a, k0, k1;
+      cell_run(cell, p_lo, np, sigma_s, size_cells, &a, &k0, &k1);
       first = k0 < 0 ? a : k0;
       if (k0 >= 0) atomicMax(&s_nmax, k1 - k0 + 1);
     }
@@ -581,11 +602,19 @@ int launch_tiles(const TL* lum, const T* rgb, T* out, int* tab, int width, int h
                sigma_r, tiles_x, ntiles, L);                                                                                                      \
   } while (0)
   if constexpr (MODE == 3) {
-    // the constant-geometry flavour where the planned geometry is exactly its own (other sigmas, VEC 1, MODE 0 - 2: as planned)
+    // the constant-geometry flavour where the planned geometry is exactly its own (other sigmas, VEC 1, MODE 0 - 2: as planned).
+    // It holds both bodies and takes the interior one for every tile that is not at the frame's edge; TDK_BILATERAL_GENERAL_BODY
+    // runs the same flavour with the general body alone, under a timer name of its own.
     if (vec && !(flags & TDK_BILATERAL_RUNTIME_GEOMETRY) && GeomDefault::equals(d, L)) {
-      TDK_MAX_LDS_ONCE((bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault>), "tdk_bilateral(hipFuncSetAttribute)");
-      TDK_LAUNCH("tdk_bilateral(tiles,const)", (bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault>), grid, dim3(FNT), lds_bytes, s, lum, rgb, out, tab,
-                 width, height, d, sigma_r, tiles_x, ntiles, L);
+      if (flags & TDK_BILATERAL_GENERAL_BODY) {
+        TDK_MAX_LDS_ONCE((bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault>), "tdk_bilateral(hipFuncSetAttribute)");
+        TDK_LAUNCH("tdk_bilateral(tiles,const,general)", (bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault>), grid, dim3(FNT), lds_bytes, s, lum, rgb, out,
+                   tab, width, height, d, sigma_r, tiles_x, ntiles, L);
+      } else {
+        TDK_MAX_LDS_ONCE((bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault, true>), "tdk_bilateral(hipFuncSetAttribute)");
+        TDK_LAUNCH("tdk_bilateral(tiles,const)", (bt_fast::bilateral_tile_kernel<TL, T, 3, 4, GeomDefault, true>), grid, dim3(FNT), lds_bytes, s, lum, rgb, out,
+                   tab, width, height, d, sigma_r, tiles_x, ntiles, L);
+      }
     } else if (vec) TDK_BT(bt_fast, 4);
     else TDK_BT(bt_fast, 1);
   }
@@ -713,7 +742,8 @@ TDK_EXPORT int tdk_bilateral_lab(const float* lum_in, const float* ab_in, void* 
   TDK_REQUIRE(lum_in && ab_in && rgb_out && workspace, "tdk_bilateral_lab: null pointer");
   TDK_REQUIRE(width > 0 && height > 0, "Invalid dimensions");
   TDK_REQUIRE(sigma_s > 0.0f && sigma_r > 0.0f, "tdk_bilateral_lab: sigmas must be positive");
-  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH | TDK_BILATERAL_RUNTIME_GEOMETRY)) == 0, "tdk_bilateral_lab: unknown flags 0x%x", flags);
+  TDK_REQUIRE((flags & ~(TDK_BILATERAL_PREPARED | TDK_BILATERAL_GENERAL_PATH | TDK_BILATERAL_RUNTIME_GEOMETRY | TDK_BILATERAL_GENERAL_BODY)) == 0,
+              "tdk_bilateral_lab: unknown flags 0x%x", flags);
   TDK_DISPATCH_DTYPE(out_dtype, T, return launch_lab<T>(lum_in, ab_in, rgb_out, workspace, width, height, sigma_s, sigma_r, detail, flags, tdk_stream(stream)));
   return TDK_OK;
 }
@@ -732,6 +762,53 @@ TDK_EXPORT int tdk_bilateral_tile_geometry(int width, int height, float sigma_s,
   if (!plan_tiles(width, height, d, sigma_s, sigma_r, 0.0f, &L, &lds_bytes, minimal)) return TDK_OK;  // the four-kernel path
   const int ps[TDK_BILATERAL_GEOMETRY_WORDS] = {1, C::equals(d, L) ? 1 : 0, d.sz, L.rs, L.plane, L.usize, L.lw, L.lh, L.ncx, L.ncy, L.hx, L.hy};
   for (int i = 0; i < TDK_BILATERAL_GEOMETRY_WORDS; i++) planned[i] = ps[i];
+  return TDK_OK;
+}
+
+// Host only: which tiles of an image the constant-geometry kernel runs its interior body on.  record_header gives the header
+// values (c_lo, nc, nmax) bilateral_axis_tables_kernel writes for one tile column or row, by the kernel's own helpers (axis_tile,
+// cell_run); the rule on them is the kernel's (axis_header_is_interior).
+static void record_header(int p0, int tile, int size_px, int size_cells, float sigma_s, int halo, int lp, int* c_lo, int* nc, int* nmax_out) {
+  const AxisTile t = axis_tile(p0, tile, size_px, size_cells, sigma_s);
+  const int p_lo = win_lo(p0, halo), np = win_np(p_lo, lp, size_px);
+  int nmax = 1;
+  for (int l = 0; l < t.nc; l++) {
+    const int cell = t.c_lo + l;
+    if (cell < 0 || cell >= size_cells) continue;
+    int a, k0, k1;
+    cell_run(cell, p_lo, np, sigma_s, size_cells, &a, &k0, &k1);
+    if (k0 >= 0) nmax = std::max(nmax, k1 - k0 + 1);
+  }
+  *c_lo = t.c_lo; *nc = t.nc; *nmax_out = std::min(nmax, std::min(TAB_W, np));
+}
+
+static bool axis_is_interior(int ti, int tile, int size_px, int size_cells, float sigma_s, int nc, int halo, int lp, int nm) {
+  int c_lo, rnc, nmax;
+  record_header(ti * tile, tile, size_px, size_cells, sigma_s, halo, lp, &c_lo, &rnc, &nmax);
+  return axis_header_is_interior(c_lo, rnc, nmax, ti * tile, size_cells, size_px, nc, nm, halo, lp);
+}
+
+TDK_EXPORT int tdk_bilateral_tile_interior(int width, int height, float sigma_s, float sigma_r, int counts[TDK_BILATERAL_INTERIOR_WORDS], unsigned char* columns,
+                                           unsigned char* rows) {
+  TDK_REQUIRE(width > 0 && height > 0 && sigma_s > 0.0f && sigma_r > 0.0f && counts, "tdk_bilateral_tile_interior: invalid arguments");
+  using C = GeomDefault;
+  const int tiles_x = tdk_div_up(width, FTW), tiles_y = tdk_div_up(height, FTH);
+  const GridDims d = compute_grid_size(width, height, sigma_s, sigma_r);
+  TileLds L;
+  size_t lds_bytes = 0;
+  const bool constant = plan_tiles(width, height, d, sigma_s, sigma_r, 0.0f, &L, &lds_bytes) && C::equals(d, L);
+  int nx = 0, ny = 0;
+  for (int i = 0; i < tiles_x; i++) {
+    const bool in = constant && axis_is_interior(i, FTW, width, d.sx, sigma_s, C::ncx, C::hx, C::lw, C::nmx);
+    if (columns) columns[i] = in;
+    nx += in;
+  }
+  for (int i = 0; i < tiles_y; i++) {
+    const bool in = constant && axis_is_interior(i, FTH, height, d.sy, sigma_s, C::ncy, C::hy, C::lh, C::nmy);
+    if (rows) rows[i] = in;
+    ny += in;
+  }
+  counts[0] = tiles_x; counts[1] = tiles_y; counts[2] = nx; counts[3] = ny; counts[4] = nx * ny;
   return TDK_OK;
 }
 

@@ -23,6 +23,15 @@ extern "C" {
 int tdk_bilateral_tile_geometry(int width, int height, float sigma_s, float sigma_r, int planned[TDK_BILATERAL_GEOMETRY_WORDS], int minimal[6],
                                 int constant[TDK_BILATERAL_GEOMETRY_WORDS]);
 
+/* Which tiles run the interior body of the constant-geometry kernel (csrc/tdk_bilateral_tile.h: tile_is_interior): a tile whose
+ * two axis records and sample window are the constant ones, so that no guard against the frame's edge can bind.  The test is
+ * separable.  counts: tile columns, tile rows, interior columns, interior rows, interior tiles (their product); all of the last
+ * three are 0 where the constant-geometry kernel is not the one planned.  columns / rows (each may be NULL): one byte per tile
+ * column / row, 1 = interior. */
+#define TDK_BILATERAL_INTERIOR_WORDS 5
+int tdk_bilateral_tile_interior(int width, int height, float sigma_s, float sigma_r, int counts[TDK_BILATERAL_INTERIOR_WORDS], unsigned char* columns,
+                                unsigned char* rows);
+
 #ifdef __cplusplus
 }
 #endif

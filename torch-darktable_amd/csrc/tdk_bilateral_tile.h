@@ -10,6 +10,11 @@
 // and the two geometry flavours GeomRuntime / GeomConst (the kernel's last template parameter): the LDS grid's shape either read from
 // the kernel arguments or known to the compiler.  Only integer addressing and control flow differ between the two; every
 // floating-point expression is the same, in the same order, so both give the same bits.
+// The phases are one body, bilateral_tile_body<..., IN>.  IN = false is the general body: every phase guards against the frame's
+// edge on per-tile runtime values (cell counts, window clipping, record starts, run lengths).  IN = true (constant geometry only)
+// is the interior body: for a tile whose records and window are the constant ones every such guard is true by construction, so
+// each becomes a compile-time constant, every trip count is known and the blur chunks unroll without a compare per cell.  No
+// floating-point expression differs.  A kernel compiled with INNER selects the body per workgroup (tile_is_interior).
 
 // The NX candidate pixels per row of one cell column, nmy rows: raster order, each pixel adds its two z
 // contributions to the column (read both cells, then write both: one LDS round trip per pixel).
@@ -83,13 +88,10 @@ __device__ __forceinline__ void sample_gz(const float (&v)[N], float (&g)[N], fl
 // MODE 0: luminance plane in (TL == T) -> filtered plane out; 1 / 2: fp32 plane + RGB in -> RGB out (linear / log);
 // 3: fp32 plane + the pixels' Lab chroma (a, b: two floats per pixel, passed through the `rgb` pointer) in -> RGB out: the Lab
 // hand-over chain (color.hip: lum_lab_extract) -- modify_luminance without its RGB -> Lab half
-template <typename TL, typename T, int MODE, int VEC, typename G = GeomRuntime>
-#ifndef TDK_BIL_WPE
-#define TDK_BIL_WPE 8  // waves per SIMD the register budget is set for (experiments: co-residency with other frames' kernels)
-#endif
-__global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE, TDK_BIL_WPE))) void bilateral_tile_kernel(
-    const TL* __restrict__ lum, const T* __restrict__ rgb, T* __restrict__ out, const int* __restrict__ tab, int width, int height, GridDims d,
-    float sigma_r, int tiles_x, int ntiles, TileLds L) {
+template <typename TL, typename T, int MODE, int VEC, typename G, bool IN>
+__device__ __forceinline__ void bilateral_tile_body(const TL* __restrict__ lum, const T* __restrict__ rgb, T* __restrict__ out, const int* __restrict__ tab,
+                                                    int width, int height, GridDims d, float sigma_r, int tiles_x, int tile, TileLds L) {
+  static_assert(!IN || (G::is_const && VEC == 4), "the interior body needs the constant geometry and the vector loads");
   extern __shared__ float smem[];
   const G geo(d, L);
 #ifdef TDK_BIL_TIMING
@@ -102,17 +104,14 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
   int* TX = reinterpret_cast<int*>(U + geo.lw * geo.lh);  // (tail of U, dead before the blur) x record: start[ncx] then weights[ncx][TAB_W]
   int* TY = TX + geo.ncx * (1 + TAB_W);
 
-  // consecutive workgroup ids go round-robin over the 8 XCDs: give each XCD a contiguous run of tiles
-  const int chunk = gridDim.x >> 3;
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-  if (tile >= ntiles) return;
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   const int x0 = txi * FTW, y0 = tyi * FTH;
   const int recx = tab_rec(geo.lw, geo.ncx), recy = tab_rec(geo.lh, geo.ncy);
   const int* rx = tab + txi * recx;
   const int* ry = tab + tiles_x * recx + tyi * recy;
-  const int px_lo = win_lo(x0, geo.hx), py_lo = win_lo(y0, geo.hy);
-  const int npx = win_np(px_lo, geo.lw, width), npy = win_np(py_lo, geo.lh, height);
+  // (interior: the window starts its whole halo before the tile and ends inside the frame)
+  const int px_lo = IN ? x0 - geo.hx : win_lo(x0, geo.hx), py_lo = IN ? y0 - geo.hy : win_lo(y0, geo.hy);
+  const int npx = IN ? geo.lw : win_np(px_lo, geo.lw, width), npy = IN ? geo.lh : win_np(py_lo, geo.lh, height);
   const int tid = threadIdx.x;
   const int PS = geo.plane, RS = geo.rs, LWS = geo.lw;
   const float ztop = (float)(geo.sz - 1), rc_r = L.rc_r;
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
         for (int k = 0; k < NB; k++) {
           const int q = base + k * FNT;
           const int r = geo.div_qw(q), c = (q - r * qw) * 4;
-          at[k] = (q < total && c < npx) ? r * LWS + c : -1;
+          at[k] = (q < total && (IN || c < npx)) ? r * LWS + c : -1;
           if (at[k] >= 0) s4_io<TL>::load(src + (size_t)r * width + c, 0, v[k]);
         }
         if (base == tid) copy_records();  // the records ride behind the first batch of samples
@@ -179,7 +178,8 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
     }
   }
   AxisTile ax, ay;  // only the cell ranges; the pixel windows are px_lo / npx, py_lo / npy
-  ax.c_lo = rx[0]; ax.nc = rx[1]; ay.c_lo = ry[0]; ay.nc = ry[1];
+  ax.c_lo = rx[0]; ay.c_lo = ry[0];
+  ax.nc = IN ? geo.ncx : rx[1]; ay.nc = IN ? geo.ncy : ry[1];
   const int nmx = rx[2], nmy = ry[2];
   BIL_MARK(8);
   lds_barrier();
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
       const int xa = TX[lx], ya = TY[ly];
       float* acc = A + c;
       for (int z = 0; z < geo.sz; z++) acc[z * PS] = 0.0f;
-      if (xa < 0 || ya < 0) continue;  // cell outside the grid: stays zero
+      if (!IN && (xa < 0 || ya < 0)) continue;  // cell outside the grid: stays zero
       const float* urow = U + ya * LWS + xa;
       const float* wxp = WX + lx;
       const float* wyp = WY + ly;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
       // disagrees (it cannot in an image of more than a few pixels) takes the general selection below
       bool splat_done = false;
       if constexpr (G::is_const) {
-        if (nmx == G::nmx && nmy == G::nmy) {
+        if (IN || (nmx == G::nmx && nmy == G::nmy)) {
           splat_column<G::nmx>(acc, urow, wxp, geo.ncx, wyp, geo.ncy, G::nmy, LWS, PS, geo.sz, contrib);
           splat_done = true;
         }
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
   constexpr int GW = FTW / VEC;
   for (int g = tid; g < GW * FTH; g += FNT) {
     const int py = g / GW, y = y0 + py, x = x0 + (g - py * GW) * VEC;
-    if (x >= width || y >= height) continue;
+    if (!IN && (x >= width || y >= height)) continue;
     const size_t i0 = (size_t)y * width + x;
     float Lv[VEC], o[MODE == 0 ? VEC : 3 * VEC], c2[MODE == 3 ? 2 * VEC : 1];
     if constexpr (VEC == 4) {
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
       else if constexpr (MODE != 0) { o[0] = ld(rgb, i0 * 3); o[1] = ld(rgb, i0 * 3 + 1); o[2] = ld(rgb, i0 * 3 + 2); }
     }
     const float gy = gys[y - py_lo];
-    const int iy = min((int)gy, d.sy - 2);
+    const int iy = IN ? (int)gy : min((int)gy, d.sy - 2);  // (interior: the tile's cells end below the grid's last one)
     const float by = gy - (float)iy, ayw = 1.0f - by;
     const float* grow = A + (iy - ay.c_lo) * RS - ax.c_lo;
     float gzv[VEC];
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
     for (int k = 0; k < VEC; k++) {
       const float Lp = Lv[k];
       const float gx = gxs[x + k - px_lo];
-      const int ix = min((int)gx, d.sx - 2);
+      const int ix = IN ? (int)gx : min((int)gx, d.sx - 2);
       const float bx = gx - (float)ix, axw = 1.0f - bx;
       const float gz = gzv[k];
       const int iz = min((int)gz, geo.sz - 2);
@@ -375,4 +375,41 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE
     }
   }
   BIL_MARK(5);
+}
+
+// Workgroup-uniform: the tile's two records and its window are the constant geometry's, so the interior body applies.  The
+// rule itself is axis_header_is_interior (bilateral.hip), per axis, on the records' header words c_lo, nc, nmax.
+template <typename G>
+__device__ __forceinline__ bool tile_is_interior(const int* __restrict__ rx, const int* __restrict__ ry, int x0, int y0, int width, int height, GridDims d) {
+  if constexpr (G::is_const) {
+    return axis_header_is_interior(rx[0], rx[1], rx[2], x0, d.sx, width, G::ncx, G::nmx, G::hx, G::lw) &&
+           axis_header_is_interior(ry[0], ry[1], ry[2], y0, d.sy, height, G::ncy, G::nmy, G::hy, G::lh);
+  }
+  return false;
+}
+
+// INNER: the kernel also holds the interior body and takes it for the tiles tile_is_interior accepts (the benchmarked
+// instantiation: bt_fast, MODE 3, VEC 4, GeomConst); without it the kernel is the general body alone.
+template <typename TL, typename T, int MODE, int VEC, typename G = GeomRuntime, bool INNER = false>
+#ifndef TDK_BIL_WPE
+#define TDK_BIL_WPE 8  // waves per SIMD the register budget is set for (experiments: co-residency with other frames' kernels)
+#endif
+__global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(TDK_BIL_WPE, TDK_BIL_WPE))) void bilateral_tile_kernel(
+    const TL* __restrict__ lum, const T* __restrict__ rgb, T* __restrict__ out, const int* __restrict__ tab, int width, int height, GridDims d,
+    float sigma_r, int tiles_x, int ntiles, TileLds L) {
+  // consecutive workgroup ids go round-robin over the 8 XCDs: give each XCD a contiguous run of tiles
+  const int chunk = gridDim.x >> 3;
+  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (tile >= ntiles) return;
+  if constexpr (INNER) {
+    const G geo(d, L);
+    const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
+    const int* rx = tab + txi * tab_rec(geo.lw, geo.ncx);
+    const int* ry = tab + tiles_x * tab_rec(geo.lw, geo.ncx) + tyi * tab_rec(geo.lh, geo.ncy);
+    if (tile_is_interior<G>(rx, ry, txi * FTW, tyi * FTH, width, height, d)) {
+      bilateral_tile_body<TL, T, MODE, VEC, G, true>(lum, rgb, out, tab, width, height, d, sigma_r, tiles_x, tile, L);
+      return;
+    }
+  }
+  bilateral_tile_body<TL, T, MODE, VEC, G, false>(lum, rgb, out, tab, width, height, d, sigma_r, tiles_x, tile, L);
 }

@@ -55,23 +55,28 @@ class BayerPattern(enum.IntEnum):
 # the four-kernel path instead of the LDS tile kernel).  The library selects per call (the `flags` of tdk_rcd_ex /
 # tdk_bilateral_ex); this thread-local context is how the GPU tests ask for the other path.  Nothing is process-global.
 TDK_RCD_TILE_KERNEL, TDK_RCD_CONCURRENT, TDK_RCD_EXACT, TDK_BILATERAL_PREPARED, TDK_BILATERAL_GENERAL_PATH, TDK_BILATERAL_RUNTIME_GEOMETRY = 1, 2, 4, 1, 2, 4
+TDK_BILATERAL_GENERAL_BODY = 8  # taken by tdk_bilateral_lab only
 _verify = threading.local()
 
 
 @contextlib.contextmanager
-def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False, rcd_exact: bool = False, bilateral_runtime_geometry: bool = False):
+def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False, rcd_exact: bool = False, bilateral_runtime_geometry: bool = False,
+                       bilateral_general_body: bool = False):
   """Inside the context (this thread only) RCD.process takes the tile kernel and / or Bilateral the four-kernel path.
   rcd_exact: a float16 result of RCD.process is the exact flavour's result rounded once (TDK_RCD_EXACT) instead of the default
   approximate arithmetic of the column strips (include/tdk_hip.h); float32 results are always exact.
   bilateral_runtime_geometry: Bilateral.process_lab runs the tile kernel that reads its grid geometry from its arguments where the
-  one compiled for the default sigmas' geometry would run (TDK_BILATERAL_RUNTIME_GEOMETRY: the same bits)."""
-  old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0))
+  one compiled for the default sigmas' geometry would run (TDK_BILATERAL_RUNTIME_GEOMETRY: the same bits).
+  bilateral_general_body: where Bilateral.process_lab runs that constant-geometry kernel, every tile takes its general body, also
+  the tiles off the frame's edge that would take the interior body (TDK_BILATERAL_GENERAL_BODY: the same bits)."""
+  old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0), getattr(_verify, 'bil_lab', 0))
   _verify.rcd = (TDK_RCD_TILE_KERNEL if rcd_tiles else 0) | (TDK_RCD_EXACT if rcd_exact else 0)
   _verify.bil = (TDK_BILATERAL_GENERAL_PATH if bilateral_general else 0) | (TDK_BILATERAL_RUNTIME_GEOMETRY if bilateral_runtime_geometry else 0)
+  _verify.bil_lab = TDK_BILATERAL_GENERAL_BODY if bilateral_general_body else 0  # the Lab entry point's own flag
   try:
     yield
   finally:
-    _verify.rcd, _verify.bil = old
+    _verify.rcd, _verify.bil, _verify.bil_lab = old
 
 
 @contextlib.contextmanager
@@ -861,7 +866,7 @@ class Bilateral(_Workspace):
     with torch.cuda.device(luminance.device):
       ws, flags = self._prepared_workspace(lib.tdk_bilateral_rgb_workspace_bytes(self._width, self._height, self._sigma_s, self._sigma_r), luminance.device)
       check(lib.tdk_bilateral_lab(_ptr(luminance), _ptr(chroma), _ptr(out), _ptr(ws), self._width, self._height, self._sigma_s, self._sigma_r, float(detail),
-                                  _dtype_tag(out), flags, _stream()))
+                                  _dtype_tag(out), flags | getattr(_verify, 'bil_lab', 0), _stream()))
     if metrics is not None:
       metrics.add(out)
     return out
