@@ -9,36 +9,16 @@ from pathlib import Path
 
 import pytest
 
+from abi_header import ctype_of, declarations, signature_tables_except
+
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_ext.h'
 EXPECTED = ['tdk_ext_abi_version', 'tdk_jpeg_device_max_stream_bytes', 'tdk_jpeg_device_workspace_bytes', 'tdk_jpeg_encode_device',
             'tdk_jpeg_huffman_tables']
 
 
-def _text():
-    return re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-
-
-def _declarations():
-    """{name: (return type, [parameter declarations])}"""
-    out = {}
-    for ret, name, args in re.findall(r'\b(int|size_t)\s+(tdk_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;', _text(), flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = (ret, [] if args in ('', 'void') else [a.strip() for a in args.split(',')])
-    return out
-
-
-def _ctype_of(decl):
-    if '*' in decl or decl.startswith('tdk_stream_t'):
-        return ctypes.c_void_p
-    for prefix, ct in (('size_t', ctypes.c_size_t), ('int64_t', ctypes.c_int64), ('int', ctypes.c_int)):
-        if decl.split()[0] == prefix:
-            return ct
-    raise AssertionError(decl)
-
-
 def test_header_declares_the_device_jpeg_surface():
-    assert sorted(_declarations()) == EXPECTED
+    assert sorted(declarations(HEADER)) == EXPECTED
     assert re.search(r'#define TDK_EXT_ABI_VERSION 1\b', HEADER.read_text())
 
 
@@ -53,13 +33,13 @@ def test_library_exports_every_ext_symbol(td):
 def test_ext_ctypes_table_matches_header(td):
     from torch_darktable import _native
 
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(_native.EXT_SIGNATURES) == sorted(decls)
-    assert not set(_native.EXT_SIGNATURES) & set(_native.SIGNATURES)
+    assert not set(_native.EXT_SIGNATURES) & signature_tables_except('EXT_SIGNATURES')
     for name, (restype, argtypes) in _native.EXT_SIGNATURES.items():
         ret, params = decls[name]
         assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [_ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
+        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
 
 
 def test_device_jpeg_size_queries_run_on_the_host(td):

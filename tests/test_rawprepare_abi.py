@@ -10,6 +10,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_raw.h'
 EXPECTED = ['tdk_raw_abi_version', 'tdk_raw_prepare', 'tdk_raw_prepare_lds_bytes']
@@ -18,24 +20,8 @@ PACKED12, PACKED12_IDS, U16, RAW_F32, RAW_F16 = range(5)
 RGGB = 0x94949494
 
 
-def _declarations():
-    """{name: (return type, [parameter declarations])}"""
-    text = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r'\b(int|size_t)\s+(tdk_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;', text, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = (ret, [] if args in ('', 'void') else [a.strip() for a in args.split(',')])
-    return out
-
-
-def _ctype_of(decl):
-    if '*' in decl or decl.startswith('tdk_stream_t'):
-        return ctypes.c_void_p
-    return {'size_t': ctypes.c_size_t, 'int': ctypes.c_int, 'float': ctypes.c_float, 'uint32_t': ctypes.c_uint32}[decl.split()[0]]
-
-
 def test_header_declares_the_raw_surface():
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
     assert re.search(r'#define TDK_RAW_ABI_VERSION 1\b', text)
@@ -65,26 +51,20 @@ def test_library_exports_every_raw_symbol(td):
 def test_raw_ctypes_table_matches_header(td):
     from torch_darktable import _native
 
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(_native.RAW_SIGNATURES) == sorted(decls)
-    others = (set(_native.SIGNATURES) | set(_native.EXT_SIGNATURES) | set(_native.DENOISE_SIGNATURES) | set(_native.RESAMPLE_SIGNATURES)
-              | set(_native.WARP_SIGNATURES))
-    assert not set(_native.RAW_SIGNATURES) & others
+    assert not set(_native.RAW_SIGNATURES) & signature_tables_except('RAW_SIGNATURES')
     for name, (restype, argtypes) in _native.RAW_SIGNATURES.items():
         ret, params = decls[name]
         assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [_ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
+        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
         assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_RAW_PACKED12, _native.TDK_RAW_PACKED12_IDS, _native.TDK_RAW_U16, _native.TDK_RAW_F32, _native.TDK_RAW_F16) == (0, 1, 2, 3, 4)
     assert (_native.TDK_RAW_HOT, _native.TDK_RAW_DEAD) == (1, 2)
 
 
 def test_the_header_is_part_of_the_source_hash():
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location('tdk_build_for_test', ROOT / 'torch-darktable_amd' / 'build.py')
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
+    build = load_build_module()
     assert HEADER in build.HEADERS and HEADER in build._inputs()
 
 

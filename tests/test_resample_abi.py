@@ -9,30 +9,16 @@ from pathlib import Path
 
 import pytest
 
+from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_resample.h'
 EXPECTED = ['tdk_resample', 'tdk_resample_abi_version', 'tdk_resample_lds_bytes']
 F32, F16, U8 = 0, 1, 2
 
 
-def _declarations():
-    """{name: (return type, [parameter declarations])}"""
-    text = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r'\b(int|size_t)\s+(tdk_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;', text, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = (ret, [] if args in ('', 'void') else [a.strip() for a in args.split(',')])
-    return out
-
-
-def _ctype_of(decl):
-    if '*' in decl or decl.startswith('tdk_stream_t'):
-        return ctypes.c_void_p
-    return {'size_t': ctypes.c_size_t, 'int': ctypes.c_int, 'float': ctypes.c_float}[decl.split()[0]]
-
-
 def test_header_declares_the_resample_surface():
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
     assert re.search(r'#define TDK_RESAMPLE_ABI_VERSION 1\b', text)
@@ -56,23 +42,19 @@ def test_library_exports_every_resample_symbol(td):
 def test_resample_ctypes_table_matches_header(td):
     from torch_darktable import _native
 
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(_native.RESAMPLE_SIGNATURES) == sorted(decls)
-    assert not set(_native.RESAMPLE_SIGNATURES) & (set(_native.SIGNATURES) | set(_native.EXT_SIGNATURES) | set(_native.DENOISE_SIGNATURES))
+    assert not set(_native.RESAMPLE_SIGNATURES) & signature_tables_except('RESAMPLE_SIGNATURES')
     for name, (restype, argtypes) in _native.RESAMPLE_SIGNATURES.items():
         ret, params = decls[name]
         assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [_ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
+        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
         assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_F32, _native.TDK_F16, _native.TDK_U8) == (F32, F16, U8)
 
 
 def test_the_header_is_part_of_the_source_hash():
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location('tdk_build_for_test', ROOT / 'torch-darktable_amd' / 'build.py')
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
+    build = load_build_module()
     assert HEADER in build.HEADERS and HEADER in build._inputs()
 
 

@@ -9,6 +9,8 @@ from pathlib import Path
 
 import pytest
 
+from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_sharpen.h'
 EXPECTED = ['tdk_sharpen', 'tdk_sharpen_abi_version', 'tdk_sharpen_lds_bytes', 'tdk_sharpen_weights']
@@ -16,24 +18,8 @@ F32, F16, U8 = 0, 1, 2
 LUMA, LIMIT = 1, 2
 
 
-def _declarations():
-    """{name: (return type, [parameter declarations])}"""
-    text = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r'\b(int|size_t)\s+(tdk_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;', text, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = (ret, [] if args in ('', 'void') else [a.strip() for a in args.split(',')])
-    return out
-
-
-def _ctype_of(decl):
-    if '*' in decl or decl.startswith('tdk_stream_t'):
-        return ctypes.c_void_p
-    return {'size_t': ctypes.c_size_t, 'int': ctypes.c_int, 'float': ctypes.c_float}[decl.split()[0]]
-
-
 def test_header_declares_the_sharpen_surface():
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
     assert re.search(r'#define TDK_SHARPEN_ABI_VERSION 1\b', text)
@@ -60,25 +46,19 @@ def test_library_exports_every_sharpen_symbol(td):
 def test_sharpen_ctypes_table_matches_header(td):
     from torch_darktable import _native
 
-    decls = _declarations()
+    decls = declarations(HEADER)
     assert sorted(_native.SHARPEN_SIGNATURES) == sorted(decls)
-    others = (set(_native.SIGNATURES) | set(_native.EXT_SIGNATURES) | set(_native.DENOISE_SIGNATURES) | set(_native.RESAMPLE_SIGNATURES)
-              | set(_native.WARP_SIGNATURES) | set(_native.RAW_SIGNATURES))
-    assert not set(_native.SHARPEN_SIGNATURES) & others
+    assert not set(_native.SHARPEN_SIGNATURES) & signature_tables_except('SHARPEN_SIGNATURES')
     for name, (restype, argtypes) in _native.SHARPEN_SIGNATURES.items():
         ret, params = decls[name]
         assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [_ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
+        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
         assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_SHARPEN_LUMA, _native.TDK_SHARPEN_LIMIT, _native.TDK_SHARPEN_MAX_RADIUS) == (LUMA, LIMIT, 12)
 
 
 def test_the_header_is_part_of_the_source_hash():
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location('tdk_build_for_test', ROOT / 'torch-darktable_amd' / 'build.py')
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
+    build = load_build_module()
     assert HEADER in build.HEADERS and HEADER in build._inputs()
     assert len(build.HEADERS) == 7 and all(h.exists() for h in build.HEADERS)
 

@@ -18,7 +18,7 @@
 #include <math.h>
 
 #include "../../include/tdk_hip_denoise.h"
-#include "tdk_common.h"
+#include "tdk_frame.h"
 
 namespace {
 
@@ -182,9 +182,8 @@ TDK_EXPORT int tdk_nlmeans(const void* image, void* out, int width, int height, 
   TDK_REQUIRE(search_radius >= 1 && search_radius <= NLM_MAX_S, "tdk_nlmeans: search_radius %d outside 1..%d", search_radius, NLM_MAX_S);
   TDK_REQUIRE(patch_radius >= 1 && patch_radius <= NLM_MAX_P, "tdk_nlmeans: patch_radius %d outside 1..%d", patch_radius, NLM_MAX_P);
   TDK_REQUIRE(isfinite(h) && h > 0.0f, "tdk_nlmeans: h must be positive and finite");
-  const size_t bytes = (size_t)width * height * channels * (dtype == TDK_F16 ? 2 : 4);
-  const char *pi = reinterpret_cast<const char*>(image), *po = reinterpret_cast<const char*>(out);
-  TDK_REQUIRE(pi + bytes <= po || po + bytes <= pi, "tdk_nlmeans: image and out overlap (every output reads its neighbours)");
+  const size_t bytes = (size_t)width * height * channels * tdk_dtype_bytes(dtype);
+  TDK_REQUIRE(tdk_disjoint(image, bytes, out, bytes), "tdk_nlmeans: image and out overlap (every output reads its neighbours)");
   NlmArgs a;
   a.width = width;
   a.height = height;

@@ -20,7 +20,7 @@
 #include <math.h>
 
 #include "../../include/tdk_hip_raw.h"
-#include "tdk_common.h"
+#include "tdk_frame.h"
 
 namespace {
 
@@ -360,11 +360,6 @@ template <typename IN> int dispatch(const void* src, void* dst, int dst_dtype, b
   return defect ? launch<IN, __half, true>(src, dst, mask, shading, gains, a, st) : launch<IN, __half, false>(src, dst, mask, shading, gains, a, st);
 }
 
-inline bool rp_disjoint(const void* p, size_t pn, const void* q, size_t qn) {
-  const char *a = reinterpret_cast<const char*>(p), *b = reinterpret_cast<const char*>(q);
-  return a + pn <= b || b + qn <= a;
-}
-
 }  // namespace
 
 TDK_EXPORT int tdk_raw_abi_version(void) { return TDK_RAW_ABI_VERSION; }
@@ -402,16 +397,16 @@ TDK_EXPORT int tdk_raw_prepare(const void* src, int src_format, void* dst, int d
   }
   const size_t n = (size_t)width * height;
   const size_t src_bytes = src_format <= TDK_RAW_PACKED12_IDS ? n / 2 * 3 : src_format == TDK_RAW_F32 ? n * 4 : n * 2;
-  const size_t dst_bytes = n * (dst_dtype == TDK_F32 ? 4 : 2);
+  const size_t dst_bytes = n * tdk_dtype_bytes(dst_dtype);
   const size_t grid_bytes = shading ? (size_t)grid_width * grid_height * 4 * sizeof(float) : 0;
-  TDK_REQUIRE(rp_disjoint(src, src_bytes, dst, dst_bytes), "tdk_raw_prepare: src and dst overlap (every output reads other positions)");
-  TDK_REQUIRE(!shading || rp_disjoint(shading, grid_bytes, dst, dst_bytes), "tdk_raw_prepare: shading and dst overlap");
-  TDK_REQUIRE(!gains || rp_disjoint(gains, 3 * sizeof(float), dst, dst_bytes), "tdk_raw_prepare: gains and dst overlap");
+  TDK_REQUIRE(tdk_disjoint(src, src_bytes, dst, dst_bytes), "tdk_raw_prepare: src and dst overlap (every output reads other positions)");
+  TDK_REQUIRE(!shading || tdk_disjoint(shading, grid_bytes, dst, dst_bytes), "tdk_raw_prepare: shading and dst overlap");
+  TDK_REQUIRE(!gains || tdk_disjoint(gains, 3 * sizeof(float), dst, dst_bytes), "tdk_raw_prepare: gains and dst overlap");
   if (mask) {
-    TDK_REQUIRE(rp_disjoint(mask, n, dst, dst_bytes), "tdk_raw_prepare: mask and dst overlap");
-    TDK_REQUIRE(rp_disjoint(mask, n, src, src_bytes), "tdk_raw_prepare: mask and src overlap");
-    TDK_REQUIRE(!shading || rp_disjoint(shading, grid_bytes, mask, n), "tdk_raw_prepare: mask and shading overlap");
-    TDK_REQUIRE(!gains || rp_disjoint(gains, 3 * sizeof(float), mask, n), "tdk_raw_prepare: mask and gains overlap");
+    TDK_REQUIRE(tdk_disjoint(mask, n, dst, dst_bytes), "tdk_raw_prepare: mask and dst overlap");
+    TDK_REQUIRE(tdk_disjoint(mask, n, src, src_bytes), "tdk_raw_prepare: mask and src overlap");
+    TDK_REQUIRE(!shading || tdk_disjoint(shading, grid_bytes, mask, n), "tdk_raw_prepare: mask and shading overlap");
+    TDK_REQUIRE(!gains || tdk_disjoint(gains, 3 * sizeof(float), mask, n), "tdk_raw_prepare: mask and gains overlap");
   }
 
   RpArgs a{};

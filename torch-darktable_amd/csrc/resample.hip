@@ -17,8 +17,7 @@
 // Nothing is accumulated across lanes or workgroups: the bits do not depend on scheduling.
 #include <math.h>
 
-#include "../../include/tdk_hip_resample.h"
-#include "tdk_common.h"
+#include "tdk_frame.h"
 
 namespace {
 
@@ -27,11 +26,6 @@ constexpr int RS_MAX_SIZE = 65535, RS_MAX_RATIO = 16;
 constexpr size_t RS_LDS_LIMIT = 64 * 1024;      // the dynamic-LDS size a kernel gets without raising its limit; two workgroups per CU
 constexpr size_t RS_LDS_TARGET = 40 * 1024;     // four, where some tile gets there
 constexpr double RS_MIN_GROUPS = 1024.0;        // four workgroups for each of 256 compute units
-
-template <typename T> __device__ __forceinline__ float rs_ld(const T* p, int i) { return ld(p, (size_t)i); }
-template <> __device__ __forceinline__ float rs_ld<uint8_t>(const uint8_t* p, int i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void rs_st(T* p, size_t i, float v) { st(p, i, v); }
-template <> __device__ __forceinline__ void rs_st<uint8_t>(uint8_t* p, size_t i, float v) { p[i] = (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 255.0f)); }
 
 // The taps of output i: first source index, count, and N of the first tap (N steps by 2 n_out per tap, |N| < D for every tap).
 __host__ __device__ inline void rs_taps(int i, int n_in, int n_out, int& j0, int& cnt, int& n0) {
@@ -166,8 +160,8 @@ template <typename T, int C> __global__ __launch_bounds__(RS_THREADS) void resam
       const T* srow = stage + r * SWC;
       const int ox = e / C, c = e - ox * C;
       const int n = cx[ox], base = (jx[ox] - sx0) * C + c;
-      float acc = wx[ox] * rs_ld(srow, base);
-      for (int k = 1; k < n; k++) acc = fmaf(wx[k * TW + ox], rs_ld(srow, base + k * C), acc);
+      float acc = wx[ox] * ld(srow, (size_t)base);
+      for (int k = 1; k < n; k++) acc = fmaf(wx[k * TW + ox], ld(srow, (size_t)(base + k * C)), acc);
       inter[(y0 + r) * EW + e] = acc;
     }
     __syncthreads();
@@ -180,7 +174,7 @@ template <typename T, int C> __global__ __launch_bounds__(RS_THREADS) void resam
     const float* col = inter + (jy[oy] - sy0) * EW + e;
     float acc = wy[oy] * col[0];
     for (int k = 1; k < n; k++) acc = fmaf(wy[k * TH + oy], col[k * EW], acc);
-    rs_st(dst, ((size_t)(oy0 + oy) * a.dw + ox0) * C + e, acc);
+    st(dst, ((size_t)(oy0 + oy) * a.dw + ox0) * C + e, acc);
   }
 }
 
@@ -189,8 +183,6 @@ template <typename T, int C> int launch(const void* src, void* dst, const RsArgs
   TDK_LAUNCH("tdk_resample", (resample_kernel<T, C>), grid, dim3(RS_THREADS), a.lds, st, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst), a);
   return TDK_OK;
 }
-
-inline size_t rs_esz(int dtype) { return dtype == TDK_F32 ? 4 : dtype == TDK_F16 ? 2 : 1; }
 
 // 0: fine; otherwise which argument is wrong (messages in tdk_resample)
 int rs_check(int sw, int sh, int dw, int dh, int channels, int dtype) {
@@ -208,7 +200,7 @@ TDK_EXPORT int tdk_resample_abi_version(void) { return TDK_RESAMPLE_ABI_VERSION;
 
 TDK_EXPORT size_t tdk_resample_lds_bytes(int src_width, int src_height, int dst_width, int dst_height, int channels, int dtype) {
   if (rs_check(src_width, src_height, dst_width, dst_height, channels, dtype) != 0) return 0;
-  return rs_plan(src_width, src_height, dst_width, dst_height, channels, rs_esz(dtype)).lds;
+  return rs_plan(src_width, src_height, dst_width, dst_height, channels, tdk_dtype_bytes(dtype)).lds;
 }
 
 TDK_EXPORT int tdk_resample(const void* src, void* dst, int src_width, int src_height, int dst_width, int dst_height, int channels, int dtype,
@@ -220,17 +212,14 @@ TDK_EXPORT int tdk_resample(const void* src, void* dst, int src_width, int src_h
   TDK_REQUIRE(bad != 3, "tdk_resample: channels must be 1 or 3, got %d", channels);
   TDK_REQUIRE(bad != 4, "tdk_resample: unsupported dtype tag %d", dtype);
   TDK_REQUIRE(bad != 5, "tdk_resample: ratio %dx%d -> %dx%d beyond %d:1 on an axis", src_width, src_height, dst_width, dst_height, RS_MAX_RATIO);
-  const size_t esz = rs_esz(dtype);
+  const size_t esz = tdk_dtype_bytes(dtype);
   const size_t src_bytes = (size_t)src_width * src_height * channels * esz, dst_bytes = (size_t)dst_width * dst_height * channels * esz;
-  const char *ps = reinterpret_cast<const char*>(src), *pd = reinterpret_cast<const char*>(dst);
-  TDK_REQUIRE(ps + src_bytes <= pd || pd + dst_bytes <= ps, "tdk_resample: src and dst overlap (every output reads its neighbours)");
+  TDK_REQUIRE(tdk_disjoint(src, src_bytes, dst, dst_bytes), "tdk_resample: src and dst overlap (every output reads its neighbours)");
   const RsArgs a = rs_plan(src_width, src_height, dst_width, dst_height, channels, esz);
   if (a.lds == 0 || a.lds > RS_LDS_LIMIT) {
     tdk_set_error("tdk_resample: no tile fits %zu bytes of LDS", RS_LDS_LIMIT);
     return TDK_ERR_INVALID_ARGUMENT;
   }
   hipStream_t st = tdk_stream(stream);
-  if (dtype == TDK_F32) return channels == 1 ? launch<float, 1>(src, dst, a, st) : launch<float, 3>(src, dst, a, st);
-  if (dtype == TDK_F16) return channels == 1 ? launch<__half, 1>(src, dst, a, st) : launch<__half, 3>(src, dst, a, st);
-  return channels == 1 ? launch<uint8_t, 1>(src, dst, a, st) : launch<uint8_t, 3>(src, dst, a, st);
+  TDK_DISPATCH_FRAME(dtype, channels, T, C, return launch<T, C>(src, dst, a, st));
 }

@@ -27,7 +27,7 @@
 #include <math.h>
 
 #include "../../include/tdk_hip_sharpen.h"
-#include "tdk_common.h"
+#include "tdk_frame.h"
 
 namespace {
 
@@ -51,26 +51,6 @@ inline size_t sh_lds_bytes(int signals, int radius) {
   return (rows * pw + rows * SH_TW) * signals * sizeof(float);
 }
 static_assert((SH_TH + 2 * SH_MAX_R) * ((SH_TW + 2 * SH_MAX_R) + SH_TW) * 3 * sizeof(float) <= SH_LDS_LIMIT, "LDS of the largest call");
-
-template <typename T> __device__ __forceinline__ float sh_ld(const T* p, size_t i) { return ld(p, i); }
-template <> __device__ __forceinline__ float sh_ld<uint8_t>(const uint8_t* p, size_t i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void sh_st(T* p, size_t i, float v) { st(p, i, v); }
-template <> __device__ __forceinline__ void sh_st<uint8_t>(uint8_t* p, size_t i, float v) { p[i] = (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 255.0f)); }
-
-// four adjacent elements at p, which is aligned to four elements
-template <typename T> __device__ __forceinline__ void sh_ld4(const T* p, float* v) { s4_io<T>::load(p, 0, v); }
-template <> __device__ __forceinline__ void sh_ld4<uint8_t>(const uint8_t* p, float* v) {
-  const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-  for (int k = 0; k < 4; k++) v[k] = (float)((u >> (8 * k)) & 0xffu);
-}
-template <typename T> __device__ __forceinline__ void sh_st4(T* p, const float* v) { s4_io<T>::store(p, 0, v); }
-template <> __device__ __forceinline__ void sh_st4<uint8_t>(uint8_t* p, const float* v) {
-  uint32_t u = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) u |= (uint32_t)rintf(fminf(fmaxf(v[k], 0.0f), 255.0f)) << (8 * k);
-  *reinterpret_cast<uint32_t*>(p) = u;
-}
 
 __device__ __forceinline__ float sh_luma(float r, float g, float b) { return (0.2126729f * r + 0.7151522f * g) + 0.0721750f * b; }
 
@@ -97,10 +77,10 @@ __global__ __launch_bounds__(SH_THREADS) void sharpen_kernel(const T* __restrict
     const int gy = min(max(y0 - R + r, 0), H - 1), gx = min(max(x0 - R + p, 0), W - 1);
     const size_t o = ((size_t)gy * W + gx) * C;
     if constexpr (LUMA) {
-      sig[it] = sh_luma(sh_ld(src, o), sh_ld(src, o + 1), sh_ld(src, o + 2));
+      sig[it] = sh_luma(ld(src, o), ld(src, o + 1), ld(src, o + 2));
     } else {
 #pragma unroll
-      for (int c = 0; c < C; c++) sig[it * C + c] = sh_ld(src, o + c);
+      for (int c = 0; c < C; c++) sig[it * C + c] = ld(src, o + c);
     }
   }
   __syncthreads();
@@ -128,10 +108,10 @@ __global__ __launch_bounds__(SH_THREADS) void sharpen_kernel(const T* __restrict
   if constexpr (LUMA) {
     if (a.vec_in) {
 #pragma unroll
-      for (int q = 0; q < C; q++) sh_ld4<T>(src + o + 4 * q, xv + 4 * q);
+      for (int q = 0; q < C; q++) s4_io<T>::load(src + o + 4 * q, 0, xv + 4 * q);   // (aligned to four elements: vec_in)
     } else {
 #pragma unroll
-      for (int i = 0; i < NX; i++) xv[i] = x + i / C < W ? sh_ld(src, o + i) : 0.0f;
+      for (int i = 0; i < NX; i++) xv[i] = x + i / C < W ? ld(src, o + i) : 0.0f;
     }
   } else {
 #pragma unroll
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(SH_THREADS) void sharpen_kernel(const T* __restrict
 #pragma unroll
           for (int c = 0; c < C; c++) {
             float v;
-            if constexpr (LUMA) v = sh_ld(src, (row + min(max(x - 1 + q, 0), W - 1)) * C + c);
+            if constexpr (LUMA) v = ld(src, (row + min(max(x - 1 + q, 0), W - 1)) * C + c);
             else v = sp[dy * SP + (q - 1) * C + c];
             cmin[q * C + c] = dy == -1 ? v : fminf(cmin[q * C + c], v);
             cmax[q * C + c] = dy == -1 ? v : fmaxf(cmax[q * C + c], v);
@@ -203,11 +183,11 @@ __global__ __launch_bounds__(SH_THREADS) void sharpen_kernel(const T* __restrict
 
   if (a.vec_out) {
 #pragma unroll
-    for (int q = 0; q < C; q++) sh_st4<T>(dst + o + 4 * q, out + 4 * q);
+    for (int q = 0; q < C; q++) s4_io<T>::store(dst + o + 4 * q, 0, out + 4 * q);
   } else {
 #pragma unroll
     for (int i = 0; i < NX; i++)
-      if (x + i / C < W) sh_st(dst, o + i, out[i]);
+      if (x + i / C < W) st(dst, o + i, out[i]);
   }
 }
 
@@ -218,12 +198,12 @@ template <typename T, int C, bool LUMA> int launch(const void* src, void* dst, c
   return TDK_OK;
 }
 
-template <typename T> int dispatch(const void* src, void* dst, int channels, bool luma, const ShArgs& a, hipStream_t st) {
-  if (channels == 1) return launch<T, 1, false>(src, dst, a, st);
-  return luma ? launch<T, 3, true>(src, dst, a, st) : launch<T, 3, false>(src, dst, a, st);
+// luma is set for three channels only (sh_check)
+template <typename T, int C> int dispatch(const void* src, void* dst, bool luma, const ShArgs& a, hipStream_t st) {
+  if constexpr (C == 3)
+    if (luma) return launch<T, 3, true>(src, dst, a, st);
+  return launch<T, C, false>(src, dst, a, st);
 }
-
-inline size_t sh_esz(int dtype) { return dtype == TDK_F32 ? 4 : dtype == TDK_F16 ? 2 : 1; }
 
 // 0: fine; otherwise which argument is wrong (messages in tdk_sharpen)
 int sh_check(int channels, int dtype, int radius, int flags) {
@@ -275,9 +255,8 @@ TDK_EXPORT int tdk_sharpen(const void* src, void* dst, int width, int height, in
   TDK_REQUIRE(amount >= 0.0f && amount <= SH_MAX_AMOUNT, "tdk_sharpen: amount must lie in [0, %g]", (double)SH_MAX_AMOUNT);
   TDK_REQUIRE(isfinite(threshold) && threshold >= 0.0f, "tdk_sharpen: threshold must be finite and >= 0");
   TDK_REQUIRE(isfinite(overshoot) && overshoot >= 0.0f, "tdk_sharpen: overshoot must be finite and >= 0");
-  const size_t esz = sh_esz(dtype), bytes = (size_t)width * height * channels * esz;
-  const char *ps = reinterpret_cast<const char*>(src), *pd = reinterpret_cast<const char*>(dst);
-  TDK_REQUIRE(ps + bytes <= pd || pd + bytes <= ps, "tdk_sharpen: src and dst overlap (every output reads its neighbours)");
+  const size_t esz = tdk_dtype_bytes(dtype), bytes = (size_t)width * height * channels * esz;
+  TDK_REQUIRE(tdk_disjoint(src, bytes, dst, bytes), "tdk_sharpen: src and dst overlap (every output reads its neighbours)");
 
   const float scale = dtype == TDK_U8 ? 255.0f : 1.0f;
   ShArgs a{};
@@ -291,7 +270,5 @@ TDK_EXPORT int tdk_sharpen(const void* src, void* dst, int width, int height, in
   a.vec_out = rows4 && tdk_aligned(dst, 4 * esz);
   const bool luma = (flags & TDK_SHARPEN_LUMA) != 0;
   hipStream_t st = tdk_stream(stream);
-  if (dtype == TDK_F32) return dispatch<float>(src, dst, channels, luma, a, st);
-  if (dtype == TDK_F16) return dispatch<__half>(src, dst, channels, luma, a, st);
-  return dispatch<uint8_t>(src, dst, channels, luma, a, st);
+  TDK_DISPATCH_FRAME(dtype, channels, T, C, return dispatch<T, C>(src, dst, luma, a, st));
 }

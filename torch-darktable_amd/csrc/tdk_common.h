@@ -123,13 +123,16 @@ __device__ __forceinline__ float sqf(float v) { return v * v; }
 __device__ __forceinline__ float mixf(float a, float b, float t) { return (1.0f - t) * a + t * b; }
 __device__ __forceinline__ float lerpf(float t, float a, float b) { return a + t * (b - a); }
 
-// Storage-type load/store: images live in HBM as float or __half, arithmetic is fp32.
+// Storage-type load/store: images live in HBM as float or __half, arithmetic is fp32.  uint8_t frames (TDK_U8: the operators of
+// tdk_frame.h) hold codes 0..255: a store clamps to that range and rounds to nearest even.
 template <typename T> __device__ __forceinline__ float ld(const T* p, size_t i);
 template <> __device__ __forceinline__ float ld<float>(const float* p, size_t i) { return p[i]; }
 template <> __device__ __forceinline__ float ld<__half>(const __half* p, size_t i) { return __half2float(p[i]); }
+template <> __device__ __forceinline__ float ld<uint8_t>(const uint8_t* p, size_t i) { return (float)p[i]; }
 template <typename T> __device__ __forceinline__ void st(T* p, size_t i, float v);
 template <> __device__ __forceinline__ void st<float>(float* p, size_t i, float v) { p[i] = v; }
 template <> __device__ __forceinline__ void st<__half>(__half* p, size_t i, float v) { p[i] = __float2half_rn(v); }
+template <> __device__ __forceinline__ void st<uint8_t>(uint8_t* p, size_t i, float v) { p[i] = (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 255.0f)); }
 
 // the value a later kernel will read back after `v` has been stored as T
 template <typename T> __device__ __forceinline__ float as_stored(float v);
@@ -206,6 +209,19 @@ template <> struct s4_io<__half> {
     u.x = *reinterpret_cast<unsigned int*>(&lo);
     u.y = *reinterpret_cast<unsigned int*>(&hi);
     reinterpret_cast<uint2*>(p)[i4] = u;
+  }
+};
+template <> struct s4_io<uint8_t> {   // one 32-bit access, bytes in ascending address order; the rounding of st<uint8_t>
+  static __device__ __forceinline__ void load(const uint8_t* p, size_t i4, float v[4]) {
+    const uint32_t u = reinterpret_cast<const uint32_t*>(p)[i4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = (float)((u >> (8 * k)) & 0xffu);
+  }
+  static __device__ __forceinline__ void store(uint8_t* p, size_t i4, const float v[4]) {
+    uint32_t u = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) u |= (uint32_t)rintf(fminf(fmaxf(v[k], 0.0f), 255.0f)) << (8 * k);
+    reinterpret_cast<uint32_t*>(p)[i4] = u;
   }
 };
 

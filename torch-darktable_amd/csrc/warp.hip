@@ -20,7 +20,7 @@
 #include <math.h>
 
 #include "../../include/tdk_hip_warp.h"
-#include "tdk_common.h"
+#include "tdk_frame.h"
 
 namespace {
 
@@ -39,11 +39,6 @@ struct WpArgs {
   int sw, sh, dw, dh;
   int border, direct;
 };
-
-template <typename T> __device__ __forceinline__ float wp_ld(const T* p, size_t i) { return ld(p, i); }
-template <> __device__ __forceinline__ float wp_ld<uint8_t>(const uint8_t* p, size_t i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void wp_st(T* p, size_t i, float v) { st(p, i, v); }
-template <> __device__ __forceinline__ void wp_st<uint8_t>(uint8_t* p, size_t i, float v) { p[i] = (uint8_t)rintf(fminf(fmaxf(v, 0.0f), 255.0f)); }
 
 // (sx, sy) of output row i, column j, before the clamp; false: the pixel is outside
 __device__ __forceinline__ bool wp_coord(const WpMap& a, int i, int j, float& sx, float& sy) {
@@ -126,12 +121,12 @@ template <int C, int INTERP, typename Fetch> __device__ __forceinline__ void wp_
 template <typename T, int C> struct WpGlobal {
   const T* src;
   int sw;
-  __device__ __forceinline__ float operator()(int x, int y, int c) const { return wp_ld(src, ((size_t)y * sw + x) * C + c); }
+  __device__ __forceinline__ float operator()(int x, int y, int c) const { return ld(src, ((size_t)y * sw + x) * C + c); }
 };
 template <typename T, int C> struct WpStaged {
   const T* stage;
   int x0, y0, pitch;   // box origin; elements per staged row
-  __device__ __forceinline__ float operator()(int x, int y, int c) const { return wp_ld(stage, (size_t)((y - y0) * pitch + (x - x0) * C + c)); }
+  __device__ __forceinline__ float operator()(int x, int y, int c) const { return ld(stage, (size_t)((y - y0) * pitch + (x - x0) * C + c)); }
 };
 
 __device__ __forceinline__ int wp_wave_min(int v) {
@@ -222,7 +217,7 @@ template <typename T, int C, int INTERP> __global__ __launch_bounds__(WP_THREADS
     if (!live[p]) continue;
     const size_t o = ((size_t)(oy0 + p * WP_ROWS) * a.dw + ox) * C;
 #pragma unroll
-    for (int c = 0; c < C; c++) wp_st(dst, o + c, inside[p] ? out[p][c] : a.fill);
+    for (int c = 0; c < C; c++) st(dst, o + c, inside[p] ? out[p][c] : a.fill);
   }
 }
 
@@ -237,18 +232,12 @@ __global__ __launch_bounds__(WP_THREADS) void warp_coordinates_kernel(float* __r
   xy[o + 1] = inside ? sy : NAN;
 }
 
-inline size_t wp_esz(int dtype) { return dtype == TDK_F32 ? 4 : dtype == TDK_F16 ? 2 : 1; }
-inline size_t wp_lds(int channels, int dtype) { return WP_RED_WORDS * sizeof(int) + (size_t)WP_BOX * channels * wp_esz(dtype); }
+inline size_t wp_lds(int channels, int dtype) { return WP_RED_WORDS * sizeof(int) + (size_t)WP_BOX * channels * tdk_dtype_bytes(dtype); }
 
 template <typename T, int C, int INTERP> int launch(const void* src, void* dst, const WpArgs& a, size_t lds, hipStream_t st) {
   const dim3 grid((unsigned)tdk_div_up(a.dw, WP_TW), (unsigned)tdk_div_up(a.dh, WP_TH));
   TDK_LAUNCH("tdk_warp", (warp_kernel<T, C, INTERP>), grid, dim3(WP_THREADS), lds, st, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst), a);
   return TDK_OK;
-}
-
-template <typename T> int dispatch(const void* src, void* dst, const WpArgs& a, int channels, int interp, size_t lds, hipStream_t st) {
-  if (channels == 1) return interp ? launch<T, 1, 1>(src, dst, a, lds, st) : launch<T, 1, 0>(src, dst, a, lds, st);
-  return interp ? launch<T, 3, 1>(src, dst, a, lds, st) : launch<T, 3, 0>(src, dst, a, lds, st);
 }
 
 inline bool wp_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= WP_MAX_SIZE && h <= WP_MAX_SIZE; }
@@ -284,10 +273,9 @@ TDK_EXPORT int tdk_warp(const void* src, void* dst, int src_width, int src_heigh
   const int bad = wp_bad_map(map);
   TDK_REQUIRE(bad < 0, "tdk_warp: map[%d] is not finite", bad);
   TDK_REQUIRE(isfinite(fill), "tdk_warp: fill is not finite");
-  const size_t esz = wp_esz(dtype);
+  const size_t esz = tdk_dtype_bytes(dtype);
   const size_t src_bytes = (size_t)src_width * src_height * channels * esz, dst_bytes = (size_t)dst_width * dst_height * channels * esz;
-  const char *ps = reinterpret_cast<const char*>(src), *pd = reinterpret_cast<const char*>(dst);
-  TDK_REQUIRE(ps + src_bytes <= pd || pd + dst_bytes <= ps, "tdk_warp: src and dst overlap (every output reads other positions)");
+  TDK_REQUIRE(tdk_disjoint(src, src_bytes, dst, dst_bytes), "tdk_warp: src and dst overlap (every output reads other positions)");
   WpArgs a{};
   for (int k = 0; k < 18; k++) a.map.m[k] = map[k];
   a.fill = fill;
@@ -295,9 +283,7 @@ TDK_EXPORT int tdk_warp(const void* src, void* dst, int src_width, int src_heigh
   a.border = border, a.direct = flags & TDK_WARP_DIRECT;
   const size_t lds = wp_lds(channels, dtype);
   hipStream_t st = tdk_stream(stream);
-  if (dtype == TDK_F32) return dispatch<float>(src, dst, a, channels, interp, lds, st);
-  if (dtype == TDK_F16) return dispatch<__half>(src, dst, a, channels, interp, lds, st);
-  return dispatch<uint8_t>(src, dst, a, channels, interp, lds, st);
+  TDK_DISPATCH_FRAME(dtype, channels, T, C, return interp ? launch<T, C, 1>(src, dst, a, lds, st) : launch<T, C, 0>(src, dst, a, lds, st));
 }
 
 TDK_EXPORT int tdk_warp_coordinates(float* xy, int dst_width, int dst_height, const float* map, tdk_stream_t stream) {

@@ -141,6 +141,19 @@ SHARPEN_SIGNATURES = {
   'tdk_sharpen_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
 }
 
+ALL_SIGNATURES = (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES)
+
+# the version function of each header -> (the version this package was written against, its name in the ImportError)
+ABI_VERSIONS = {
+  'tdk_abi_version': (4, 'ABI'),
+  'tdk_ext_abi_version': (1, 'extension ABI'),
+  'tdk_denoise_abi_version': (1, 'denoise ABI'),
+  'tdk_resample_abi_version': (1, 'resample ABI'),
+  'tdk_warp_abi_version': (1, 'warp ABI'),
+  'tdk_raw_abi_version': (1, 'raw ABI'),
+  'tdk_sharpen_abi_version': (1, 'sharpen ABI'),
+}
+
 TDK_F32, TDK_F16 = 0, 1
 TDK_U8 = 2  # include/tdk_hip_resample.h: taken by tdk_resample and tdk_warp only
 TDK_WARP_DIRECT = 1  # include/tdk_hip_warp.h: flags of tdk_warp
@@ -158,25 +171,14 @@ def load() -> C.CDLL:
       'torch_darktable has no CPU or pure-PyTorch fallback.'
     )
   lib = C.CDLL(str(_LIB_PATH))
-  for table in (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES):
+  for table in ALL_SIGNATURES:
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)  # AttributeError here == ABI mismatch between header and library
       fn.restype = restype
       fn.argtypes = argtypes
-  if lib.tdk_abi_version() != 4:
-    raise ImportError(f'libtdk_hip.so ABI version {lib.tdk_abi_version()} != 4')
-  if lib.tdk_ext_abi_version() != 1:
-    raise ImportError(f'libtdk_hip.so extension ABI version {lib.tdk_ext_abi_version()} != 1')
-  if lib.tdk_denoise_abi_version() != 1:
-    raise ImportError(f'libtdk_hip.so denoise ABI version {lib.tdk_denoise_abi_version()} != 1')
-  if lib.tdk_resample_abi_version() != 1:
-    raise ImportError(f'libtdk_hip.so resample ABI version {lib.tdk_resample_abi_version()} != 1')
-  if lib.tdk_warp_abi_version() != 1:
-    raise ImportError(f'libtdk_hip.so warp ABI version {lib.tdk_warp_abi_version()} != 1')
-  if lib.tdk_raw_abi_version() != 1:
-    raise ImportError(f'libtdk_hip.so raw ABI version {lib.tdk_raw_abi_version()} != 1')
-  if lib.tdk_sharpen_abi_version() != 1:
-    raise ImportError(f'libtdk_hip.so sharpen ABI version {lib.tdk_sharpen_abi_version()} != 1')
+  for name, (expected, label) in ABI_VERSIONS.items():
+    if getattr(lib, name)() != expected:
+      raise ImportError(f'libtdk_hip.so {label} version {getattr(lib, name)()} != {expected}')
   return lib
 
 

@@ -18,7 +18,7 @@ import math
 
 import torch
 
-from ._native import lib
+from ._native import check, lib
 from .extension import extension
 from .torch_darktable_extension import _dtype_tag, _ptr, _require, _stream
 
@@ -73,8 +73,7 @@ class NLMeans:
             out = torch.empty_like(image)
             rc = lib.tdk_nlmeans(_ptr(image), _ptr(out), self.width, self.height, channels, tag, self.search_radius, self.patch_radius, h,
                                  ctypes.cast(weights, ctypes.c_void_p) if weights is not None else None, _stream())
-        if rc != 0:
-            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        check(rc)
         return out
 
     def process_luminance(self, image: torch.Tensor, h: float) -> torch.Tensor:

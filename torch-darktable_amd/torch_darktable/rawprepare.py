@@ -27,7 +27,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from ._native import (TDK_F16, TDK_F32, TDK_RAW_DEAD, TDK_RAW_F16, TDK_RAW_F32, TDK_RAW_HOT, TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, lib)
+from ._native import (TDK_F16, TDK_F32, TDK_RAW_DEAD, TDK_RAW_F16, TDK_RAW_F32, TDK_RAW_HOT, TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, check, lib)
 from .bayer import BayerPattern, PackedFormat
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
@@ -158,8 +158,7 @@ class RawPrepare:
                                      (TDK_RAW_HOT if self.hot else 0) | (TDK_RAW_DEAD if self.dead else 0), self.threshold, self.ratio, self.min_count,
                                      _ptr(shading), shading.size(1) if shading is not None else 0, shading.size(0) if shading is not None else 0,
                                      _ptr(gains), int(self.clip), _stream())
-        if rc != 0:
-            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        check(rc)
         return out
 
     def process(self, mosaic: torch.Tensor, white_balance=None, out_dtype: torch.dtype = torch.float32, mask_out: torch.Tensor | None = None) -> torch.Tensor:

@@ -14,22 +14,20 @@ from __future__ import annotations
 
 import torch
 
-from ._native import TDK_F16, TDK_F32, TDK_U8, lib
-from .torch_darktable_extension import _ptr, _require, _stream
+from ._frames import TAGS, check_frame, check_size, require_cuda_device
+from ._native import check, lib
+from .torch_darktable_extension import _ptr, _stream
 
-MAX_SIZE, MAX_RATIO = 65535, 16
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint8: TDK_U8}
+MAX_RATIO = 16
 
 
 class Resize:
     """Scale (H, W, C) images of one size to another; sizes are (width, height).  Shrinking is limited to 16:1 per axis."""
 
     def __init__(self, device: torch.device, input_size: tuple[int, int], output_size: tuple[int, int]):
-        if device.type != 'cuda':
-            raise ValueError(f'Device must be CUDA, got {device}')
-        for what, size in (('Input', input_size), ('Output', output_size)):
-            if not all(1 <= int(v) <= MAX_SIZE for v in size):
-                raise ValueError(f'{what} dimensions must be 1..{MAX_SIZE}, got {size[0]}x{size[1]}')
+        require_cuda_device(device)
+        check_size('Input', input_size)
+        check_size('Output', output_size)
         (self.width, self.height), (self.out_width, self.out_height) = (int(v) for v in input_size), (int(v) for v in output_size)
         if self.width > MAX_RATIO * self.out_width or self.height > MAX_RATIO * self.out_height:
             raise ValueError(f'ratio {self.width}x{self.height} -> {self.out_width}x{self.out_height} is beyond {MAX_RATIO}:1 on an axis')
@@ -55,26 +53,15 @@ class Resize:
 
     def lds_bytes(self, channels: int, dtype: torch.dtype) -> int:
         """LDS one workgroup takes for this geometry (0: not a legal call)."""
-        return int(lib.tdk_resample_lds_bytes(self.width, self.height, self.out_width, self.out_height, channels, _TAGS.get(dtype, -1)))
+        return int(lib.tdk_resample_lds_bytes(self.width, self.height, self.out_width, self.out_height, channels, TAGS.get(dtype, -1)))
 
     def process(self, image: torch.Tensor) -> torch.Tensor:
         """(height, width, C) -> (out_height, out_width, C), C in {1, 3}, float32, float16 or uint8, the same type out."""
-        assert image.dim() == 3, f'image must have 3 dimensions, got {image.shape}'
-        expected = (self.height, self.width, image.size(2))
-        if tuple(image.shape) != expected:
-            raise RuntimeError(f'Resize input shape {tuple(image.shape)} != expected {expected}')
-        channels = image.size(2)
-        if channels not in {1, 3}:
-            raise ValueError(f'image channels must be 1 or 3, got {channels}')
-        _require(image.is_cuda, 'Input must be on CUDA device')
-        _require(image.is_contiguous(), 'Input must be contiguous')
-        _require(image.dtype in _TAGS, 'Input tensor must be float32, float16 or uint8')
+        _, _, channels, tag = check_frame(image, (self.height, self.width), 'Resize')
         with torch.cuda.device(image.device):
             out = torch.empty((self.out_height, self.out_width, channels), dtype=image.dtype, device=image.device)
-            rc = lib.tdk_resample(_ptr(image), _ptr(out), self.width, self.height, self.out_width, self.out_height, channels,
-                                  _TAGS[image.dtype], _stream())
-        if rc != 0:
-            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+            rc = lib.tdk_resample(_ptr(image), _ptr(out), self.width, self.height, self.out_width, self.out_height, channels, tag, _stream())
+        check(rc)
         return out
 
 

@@ -17,11 +17,11 @@ import math
 
 import torch
 
-from ._native import TDK_F16, TDK_F32, TDK_SHARPEN_LIMIT, TDK_SHARPEN_LUMA, TDK_SHARPEN_MAX_RADIUS, TDK_U8, lib
-from .torch_darktable_extension import _ptr, _require, _stream
+from ._frames import TAGS, check_frame, require_cuda_device
+from ._native import TDK_SHARPEN_LIMIT, TDK_SHARPEN_LUMA, TDK_SHARPEN_MAX_RADIUS, check, lib
+from .torch_darktable_extension import _ptr, _stream
 
-MAX_SIZE, MAX_AMOUNT = 65535, 16.0
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint8: TDK_U8}
+MAX_AMOUNT = 16.0
 
 
 class Sharpen:
@@ -53,8 +53,7 @@ class Sharpen:
         return self
 
     def _setup(self, device, weights, amount, threshold, luma, overshoot) -> None:
-        if device.type != 'cuda':
-            raise ValueError(f'Device must be CUDA, got {device}')
+        require_cuda_device(device)
         if not 2 <= len(weights) <= TDK_SHARPEN_MAX_RADIUS + 1:
             raise ValueError(f'weights must hold 2..{TDK_SHARPEN_MAX_RADIUS + 1} values (radius 1..{TDK_SHARPEN_MAX_RADIUS}), got {len(weights)}')
         if not all(math.isfinite(w) and w >= 0.0 for w in weights):
@@ -89,25 +88,16 @@ class Sharpen:
 
     def lds_bytes(self, channels: int, dtype: torch.dtype) -> int:
         """LDS one workgroup takes on frames of this kind (0: not a legal call)."""
-        return int(lib.tdk_sharpen_lds_bytes(channels, _TAGS.get(dtype, -1), self.radius, self._flags(channels)))
+        return int(lib.tdk_sharpen_lds_bytes(channels, TAGS.get(dtype, -1), self.radius, self._flags(channels)))
 
     def process(self, image: torch.Tensor) -> torch.Tensor:
         """(H, W, C) -> (H, W, C), C in {1, 3}, float32, float16 or uint8, the same type out."""
-        assert image.dim() == 3, f'image must have 3 dimensions, got {image.shape}'
-        height, width, channels = image.shape
-        if channels not in {1, 3}:
-            raise ValueError(f'image channels must be 1 or 3, got {channels}')
-        if not (1 <= height <= MAX_SIZE and 1 <= width <= MAX_SIZE):
-            raise ValueError(f'image dimensions must be 1..{MAX_SIZE}, got {width}x{height}')
-        _require(image.is_cuda, 'Input must be on CUDA device')
-        _require(image.is_contiguous(), 'Input must be contiguous')
-        _require(image.dtype in _TAGS, 'Input tensor must be float32, float16 or uint8')
+        height, width, channels, tag = check_frame(image)
         with torch.cuda.device(image.device):
             out = torch.empty_like(image)
-            rc = lib.tdk_sharpen(_ptr(image), _ptr(out), width, height, channels, _TAGS[image.dtype], self._c_weights, self.radius, self.amount,
+            rc = lib.tdk_sharpen(_ptr(image), _ptr(out), width, height, channels, tag, self._c_weights, self.radius, self.amount,
                                  self.threshold, 0.0 if self.overshoot is None else self.overshoot, self._flags(channels), _stream())
-        if rc != 0:
-            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        check(rc)
         return out
 
 

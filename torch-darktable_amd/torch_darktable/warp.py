@@ -26,11 +26,10 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from ._native import TDK_F16, TDK_F32, TDK_U8, TDK_WARP_DIRECT, lib
-from .torch_darktable_extension import _ptr, _require, _stream
+from ._frames import TAGS, check_frame, check_size, require_cuda_device
+from ._native import TDK_WARP_DIRECT, check, lib
+from .torch_darktable_extension import _ptr, _stream
 
-MAX_SIZE = 65535
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint8: TDK_U8}
 _INTERPOLATION = {'bilinear': 0, 'bicubic': 1}
 _BORDER = {'constant': 0, 'replicate': 1}
 
@@ -47,11 +46,9 @@ class Warp:
 
     def __init__(self, device: torch.device, input_size: tuple[int, int], output_size: tuple[int, int], map: Sequence[float],
                  interpolation: str = 'bicubic', border: str = 'constant', fill: float = 0.0):
-        if device.type != 'cuda':
-            raise ValueError(f'Device must be CUDA, got {device}')
-        for what, size in (('Input', input_size), ('Output', output_size)):
-            if not all(1 <= int(v) <= MAX_SIZE for v in size):
-                raise ValueError(f'{what} dimensions must be 1..{MAX_SIZE}, got {size[0]}x{size[1]}')
+        require_cuda_device(device)
+        check_size('Input', input_size)
+        check_size('Output', output_size)
         (self.width, self.height), (self.out_width, self.out_height) = (int(v) for v in input_size), (int(v) for v in output_size)
         if interpolation not in _INTERPOLATION:
             raise ValueError(f"interpolation must be 'bilinear' or 'bicubic', got {interpolation!r}")
@@ -132,28 +129,18 @@ class Warp:
 
     def lds_bytes(self, channels: int, dtype: torch.dtype) -> int:
         """LDS one workgroup takes (0: not a legal call)."""
-        return int(lib.tdk_warp_lds_bytes(channels, _TAGS.get(dtype, -1), _INTERPOLATION[self.interpolation]))
+        return int(lib.tdk_warp_lds_bytes(channels, TAGS.get(dtype, -1), _INTERPOLATION[self.interpolation]))
 
     def process(self, image: torch.Tensor, direct: bool = False) -> torch.Tensor:
         """(height, width, C) -> (out_height, out_width, C), C in {1, 3}, float32, float16 or uint8, the same type out.
         direct=True (TDK_WARP_DIRECT) makes every tile sample from global memory: the same bits, for tests and measurement."""
-        assert image.dim() == 3, f'image must have 3 dimensions, got {image.shape}'
-        expected = (self.height, self.width, image.size(2))
-        if tuple(image.shape) != expected:
-            raise RuntimeError(f'Warp input shape {tuple(image.shape)} != expected {expected}')
-        channels = image.size(2)
-        if channels not in {1, 3}:
-            raise ValueError(f'image channels must be 1 or 3, got {channels}')
-        _require(image.is_cuda, 'Input must be on CUDA device')
-        _require(image.is_contiguous(), 'Input must be contiguous')
-        _require(image.dtype in _TAGS, 'Input tensor must be float32, float16 or uint8')
+        _, _, channels, tag = check_frame(image, (self.height, self.width), 'Warp')
         with torch.cuda.device(image.device):
             out = torch.empty((self.out_height, self.out_width, channels), dtype=image.dtype, device=image.device)
-            rc = lib.tdk_warp(_ptr(image), _ptr(out), self.width, self.height, self.out_width, self.out_height, channels, _TAGS[image.dtype],
+            rc = lib.tdk_warp(_ptr(image), _ptr(out), self.width, self.height, self.out_width, self.out_height, channels, tag,
                               ctypes.addressof(self._c_map), _INTERPOLATION[self.interpolation], _BORDER[self.border], self.fill,
                               TDK_WARP_DIRECT if direct else 0, _stream())
-        if rc != 0:
-            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        check(rc)
         return out
 
     def coordinates(self) -> torch.Tensor:
@@ -162,8 +149,7 @@ class Warp:
         with torch.cuda.device(self._device):
             xy = torch.empty((self.out_height, self.out_width, 2), dtype=torch.float32, device=self._device)
             rc = lib.tdk_warp_coordinates(_ptr(xy), self.out_width, self.out_height, ctypes.addressof(self._c_map), _stream())
-        if rc != 0:
-            raise RuntimeError(lib.tdk_last_error().decode('utf-8', 'replace'))
+        check(rc)
         return xy
 
 
