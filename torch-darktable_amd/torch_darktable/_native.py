@@ -141,7 +141,17 @@ SHARPEN_SIGNATURES = {
   'tdk_sharpen_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
 }
 
-ALL_SIGNATURES = (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES)
+# name -> (restype, argtypes); mirrors include/tdk_hip_wavelet.h, the wavelet denoiser (thresholds: a host pointer to scales * channels floats)
+WAVELET_SIGNATURES = {
+  'tdk_wavelet_abi_version': (c_int, []),
+  'tdk_wavelet_band_norms': (c_int, [c_int, c_void_p]),
+  'tdk_wavelet_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_wavelet': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+  'tdk_wavelet_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+}
+
+ALL_SIGNATURES = (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES,
+                  WAVELET_SIGNATURES)
 
 # the version function of each header -> (the version this package was written against, its name in the ImportError)
 ABI_VERSIONS = {
@@ -152,6 +162,7 @@ ABI_VERSIONS = {
   'tdk_warp_abi_version': (1, 'warp ABI'),
   'tdk_raw_abi_version': (1, 'raw ABI'),
   'tdk_sharpen_abi_version': (1, 'sharpen ABI'),
+  'tdk_wavelet_abi_version': (1, 'wavelet ABI'),
 }
 
 TDK_F32, TDK_F16 = 0, 1
@@ -162,6 +173,8 @@ TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, TDK_RAW_F32, TDK_RAW_F16 = 
 TDK_RAW_HOT, TDK_RAW_DEAD = 1, 2
 TDK_SHARPEN_LUMA, TDK_SHARPEN_LIMIT = 1, 2  # include/tdk_hip_sharpen.h: flags of tdk_sharpen
 TDK_SHARPEN_MAX_RADIUS = 12
+TDK_WAVELET_YCC = 1  # include/tdk_hip_wavelet.h: flags of tdk_wavelet
+TDK_WAVELET_MAX_SCALES = 5
 
 
 def load() -> C.CDLL:

@@ -1,4 +1,5 @@
 """packed raw bytes -> uint8 RGB: decode -> [white balance] -> demosaic -> [post-process] ->
+[wavelet chroma denoise] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  `process_resized` / `process_image_set_resized` put the
 antialiased scaler to `final_size` between the tone mapper and the sharpener; `process` / `process_image_set` ignore
@@ -20,6 +21,7 @@ from ..local_contrast import Bilateral
 from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
+from ..wavelet import Wavelet
 from ..white_balance import apply_white_balance
 from .camera_settings import CameraSettings
 from .config import Debayer, ImageProcessingSettings, ToneMapper
@@ -41,7 +43,8 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, sharpen: Sharpen | None = None, raw_correction: RawPrepare | None = None):
+                 storage_dtype: torch.dtype = torch.float32, sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
+                 raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
         self.device = device
         self.settings = settings
@@ -63,6 +66,16 @@ class ImageProcessor:
         if sharpen is not None and not isinstance(sharpen, Sharpen):
             raise TypeError(f'sharpen must be a Sharpen or None, got {type(sharpen).__name__} (raw_correction is the argument after it: pass both by keyword)')
         self.sharpen = sharpen
+        # wavelet shrinkage of every demosaiced frame (luma/chroma: the colour noise the log-lightness denoiser never sees), in
+        # front of the bounds; None: the reference's chain
+        if chroma_denoise is not None:
+            if not isinstance(chroma_denoise, Wavelet):
+                raise TypeError(f'chroma_denoise must be a Wavelet or None, got {type(chroma_denoise).__name__} (raw_correction is the argument after it: pass both by keyword)')
+            if (chroma_denoise.width, chroma_denoise.height) != tuple(image_size):
+                raise ValueError(f'chroma_denoise is for {chroma_denoise.width}x{chroma_denoise.height}, the processor for {image_size[0]}x{image_size[1]}')
+            if chroma_denoise.channels == 1:
+                raise ValueError('chroma_denoise has thresholds for one channel, the demosaiced frames have three channels')
+        self.chroma_denoise = chroma_denoise
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -260,6 +273,8 @@ class ImageProcessor:
         names = list(image_set_bytes.keys())
         ema = self.settings.moving_average
         rgb = [self.load_image(b) for b in image_set_bytes.values()]
+        if self.chroma_denoise is not None:
+            rgb = [self.chroma_denoise.process(img) for img in rgb]
         bounds = _tonemap.compute_image_bounds(rgb, stride=8)
         self.bounds = lerp(self.bounds if self.bounds is not None else bounds, bounds, ema)
         acc = _tonemap.MetricsAccumulator(self.device, stride=8)  # == compute_image_metrics(rgb, stride=8), fed by the last stage
