@@ -38,7 +38,7 @@ CXXFLAGS += os.environ.get('TDK_EXTRA_FLAGS', '').split()  # experiments: e.g. T
 HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip.h', 'tdk_hip_ext.h', 'tdk_hip_denoise.h', 'tdk_hip_resample.h', 'tdk_hip_warp.h', 'tdk_hip_raw.h',
                                                        'tdk_hip_sharpen.h')]
 # the headers added after the seven above, whose number tests/test_sharpen_abi.py pins
-LATER_HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip_wavelet.h',)]
+LATER_HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip_wavelet.h', 'tdk_hip_highlights.h')]
 
 
 def _inputs():

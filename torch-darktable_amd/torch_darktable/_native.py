@@ -150,8 +150,17 @@ WAVELET_SIGNATURES = {
   'tdk_wavelet_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_highlights.h, the highlight reconstruction (gains, chroma, stats: device pointers)
+HIGHLIGHTS_SIGNATURES = {
+  'tdk_highlights_abi_version': (c_int, []),
+  'tdk_highlights_workspace_bytes': (c_size_t, []),
+  'tdk_highlights_lds_bytes': (c_size_t, [c_int]),
+  'tdk_highlights_chrominance': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+  'tdk_highlights': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
+}
+
 ALL_SIGNATURES = (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES,
-                  WAVELET_SIGNATURES)
+                  WAVELET_SIGNATURES, HIGHLIGHTS_SIGNATURES)
 
 # the version function of each header -> (the version this package was written against, its name in the ImportError)
 ABI_VERSIONS = {
@@ -163,6 +172,7 @@ ABI_VERSIONS = {
   'tdk_raw_abi_version': (1, 'raw ABI'),
   'tdk_sharpen_abi_version': (1, 'sharpen ABI'),
   'tdk_wavelet_abi_version': (1, 'wavelet ABI'),
+  'tdk_highlights_abi_version': (1, 'highlights ABI'),
 }
 
 TDK_F32, TDK_F16 = 0, 1
@@ -175,6 +185,7 @@ TDK_SHARPEN_LUMA, TDK_SHARPEN_LIMIT = 1, 2  # include/tdk_hip_sharpen.h: flags o
 TDK_SHARPEN_MAX_RADIUS = 12
 TDK_WAVELET_YCC = 1  # include/tdk_hip_wavelet.h: flags of tdk_wavelet
 TDK_WAVELET_MAX_SCALES = 5
+TDK_HL_CLIP, TDK_HL_OPPOSED = 0, 1  # include/tdk_hip_highlights.h: mode of tdk_highlights
 
 
 def load() -> C.CDLL:

@@ -1,4 +1,4 @@
-"""packed raw bytes -> uint8 RGB: decode -> [white balance] -> demosaic -> [post-process] ->
+"""packed raw bytes -> uint8 RGB: decode -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
 [wavelet chroma denoise] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  `process_resized` / `process_image_set_resized` put the
@@ -17,6 +17,7 @@ from .. import debayer as _debayer
 from .. import tonemap as _tonemap
 from ..bayer import BayerPattern, PackedFormat
 from ..denoise import Wiener
+from ..highlights import Highlights
 from ..local_contrast import Bilateral
 from ..rawprepare import RawPrepare
 from ..resample import Resize
@@ -43,7 +44,7 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
+                 storage_dtype: torch.dtype = torch.float32, highlights: Highlights | None = None, sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
         self.device = device
@@ -76,6 +77,16 @@ class ImageProcessor:
             if chroma_denoise.channels == 1:
                 raise ValueError('chroma_denoise has thresholds for one channel, the demosaiced frames have three channels')
         self.chroma_denoise = chroma_denoise
+        # white balance that reconstructs clipped highlights, in the place of the white balance in front of the demosaic; None: the
+        # reference's chain
+        if highlights is not None:
+            if not isinstance(highlights, Highlights):
+                raise TypeError(f'highlights must be a Highlights or None, got {type(highlights).__name__} (sharpen is the argument after it: pass both by keyword)')
+            if highlights.image_size != tuple(image_size) or highlights.bayer_pattern != bayer_pattern:
+                raise ValueError(f'highlights is for {highlights.image_size} {highlights.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+            if white_balance is None:
+                raise ValueError('highlights needs white_balance: it applies the gains itself')
+        self.highlights = highlights
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -166,6 +177,18 @@ class ImageProcessor:
         return decoded.view(h, w)
 
     def load_image(self, bytes: torch.Tensor) -> torch.Tensor:
+        if self.highlights is not None:
+            # the gains are applied by the highlight stage, on the linear mosaic: sensor correction without gains (or the plain
+            # decode) -> highlights -> demosaic; the fused decode + white balance + RCD kernel has no place for it
+            if self.raw_correction is not None:
+                if bytes.numel() != self.expected_bytes:
+                    raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
+                                         f'with {self.padding} padding, got {bytes.numel()} bytes. ')
+                payload = bytes[: bytes.numel() - self.padding] if self.padding > 0 else bytes
+                mosaic = self.raw_correction.process_packed(payload, self.packed_format, white_balance=None)
+            else:
+                mosaic = self.load_bytes(bytes)
+            return self._demosaic(self.highlights.process(mosaic, self.white_balance)).to(self.storage_dtype)
         if self.raw_correction is not None:
             if bytes.numel() != self.expected_bytes:
                 raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
