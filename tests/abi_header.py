@@ -1,5 +1,5 @@
-"""What the per-header ABI tests (test_*_abi.py) share: the declarations of a C header, the ctypes type of a parameter, the build
-script as a module, and the names the other ctypes tables of torch_darktable._native already hold."""
+"""What the ABI tests (test_header_abi.py, test_*_abi.py) share: the declarations of a C header, the ctypes type of a parameter and
+the build script as a module."""
 
 import ctypes
 import importlib.util
@@ -35,11 +35,3 @@ def load_build_module():
     spec.loader.exec_module(build)
     return build
 
-
-def signature_tables_except(name):
-    """The function names of every table in _native.ALL_SIGNATURES but the one called `name` (say 'WARP_SIGNATURES')."""
-    from torch_darktable import _native
-
-    own = getattr(_native, name)
-    assert any(table is own for table in _native.ALL_SIGNATURES), name
-    return set().union(*(table for table in _native.ALL_SIGNATURES if table is not own))

@@ -8,15 +8,12 @@ of frame sizes, and reads the gfx950 metadata of the kernel that holds both bodi
 import ctypes
 import math
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'bilateral.hip'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
+from kernel_isa import device_asm, metadata
+
 FIELDS = ('tiles', 'constant', 'sz', 'rs', 'plane', 'usize', 'lw', 'lh', 'ncx', 'ncy', 'hx', 'hy')
 SIGMA_S, SIGMA_R = 2.0, 0.2
 f32 = np.float32
@@ -141,19 +138,13 @@ def test_other_sigmas_have_no_interior_tiles(lib):
 
 @pytest.fixture(scope='module')
 def asm():
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, str(SOURCE)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout
+    return device_asm('bilateral')
 
 
 def test_kernel_with_both_bodies_keeps_eight_waves_and_spills_nothing(asm):
     """Code-object metadata of bt_fast MODE 3 VEC 4 GeomConst with the interior body (last template argument true), both output
     types: 64 VGPRs at most and no AGPRs is 8 waves per SIMD of the 512-entry file; no spill, no private segment."""
-    text = asm[asm.index('amdhsa.kernels:'):asm.index('.end_amdgpu_metadata')]
-    meta = {}
-    for chunk in re.split(r'\n  - (?=\.)', text)[1:]:
-        fields = dict(re.findall(r'^\s*\.(\w+):\s+(\S+)\s*$', chunk, flags=re.M))
-        meta[fields['name']] = {k: int(v) for k, v in fields.items() if v.isdigit()}
+    meta = metadata(asm)
     both = {n: m for n, m in meta.items() if re.search(r'bt_fast21bilateral_tile_kernelIf(f|6__half)Li3ELi4ENS_9GeomConst\w+?EELb1EEE', n)}
     assert len(both) == 2, sorted(meta)
     general = {n: m for n, m in meta.items() if re.search(r'bt_fast21bilateral_tile_kernelIf(f|6__half)Li3ELi4ENS_9GeomConst\w+?EELb0EEE', n)}

@@ -1,15 +1,14 @@
-"""CPU-only: the companion header include/tdk_hip_ext.h (entry points beyond the reference's surface) -- the library exports every
-declaration, the ctypes table _native.EXT_SIGNATURES mirrors it parameter for parameter, the size queries and the argument checks of
+"""CPU-only: the companion header include/tdk_hip_ext.h (entry points beyond the reference's surface) -- it parses to exactly its
+five declarations (exports and the ctypes table: tests/test_header_abi.py), the size queries and the argument checks of
 the device-resident JPEG encode answer on the host, and the new kernels of that path keep everything in registers and LDS."""
 
-import ctypes
 import re
-import subprocess
 from pathlib import Path
 
 import pytest
 
-from abi_header import ctype_of, declarations, signature_tables_except
+from abi_header import declarations
+from kernel_isa import device_asm, metadata
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_ext.h'
@@ -17,29 +16,12 @@ EXPECTED = ['tdk_ext_abi_version', 'tdk_jpeg_device_max_stream_bytes', 'tdk_jpeg
             'tdk_jpeg_huffman_tables']
 
 
-def test_header_declares_the_device_jpeg_surface():
-    assert sorted(declarations(HEADER)) == EXPECTED
-    assert re.search(r'#define TDK_EXT_ABI_VERSION 1\b', HEADER.read_text())
-
-
-def test_library_exports_every_ext_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_ext.h but not exported'
-    lib.tdk_ext_abi_version.restype = ctypes.c_int
-    assert lib.tdk_ext_abi_version() == 1
-
-
-def test_ext_ctypes_table_matches_header(td):
+def test_header_declares_the_device_jpeg_surface(td):
     from torch_darktable import _native
 
-    decls = declarations(HEADER)
-    assert sorted(_native.EXT_SIGNATURES) == sorted(decls)
-    assert not set(_native.EXT_SIGNATURES) & signature_tables_except('EXT_SIGNATURES')
-    for name, (restype, argtypes) in _native.EXT_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
+    assert sorted(declarations(HEADER)) == EXPECTED
+    assert re.search(r'#define TDK_EXT_ABI_VERSION 1\b', HEADER.read_text())
+    assert _native.ABI_VERSIONS['tdk_ext_abi_version'] == (1, 'extension ABI')
 
 
 def test_device_jpeg_size_queries_run_on_the_host(td):
@@ -88,17 +70,7 @@ def test_device_jpeg_invalid_arguments_fail_on_the_host(td):
 def test_device_path_kernels_use_no_scratch():
     """gfx950 ISA of csrc/jpeg.hip: the table / marker kernel (both forms) and the device-position stuffing kernel keep their state in
     registers and LDS (.private_segment_fixed_size: 0) -- the K.2 loop's per-lane arrays are indexed by unrolled constants only."""
-    flags = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *flags, str(ROOT / 'torch-darktable_amd' / 'csrc' / 'jpeg.hip')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    private, name = {}, None
-    for line in r.stdout.split('\n'):   # the code-object metadata: .name precedes .private_segment_fixed_size in every kernel's map
-        m = re.match(r'\s+\.name:\s+(\S+)', line)
-        if m:
-            name = m.group(1)
-        m = re.match(r'\s+\.private_segment_fixed_size:\s+(\d+)', line)
-        if m and name:
-            private[name] = int(m.group(1))
+    private = {name: m['private_segment_fixed_size'] for name, m in metadata(device_asm('jpeg')).items()}
     wanted = {n: v for n, v in private.items() if re.search(r'jpeg_tables_kernelILb[01]E|jpeg_stuff_kernelILb1ELb1E|jpeg_scan_kernelILb1E', n)}
     assert len(wanted) == 4, sorted(private)
     assert all(v == 0 for v in wanted.values()), wanted

@@ -1,17 +1,16 @@
-"""CPU-only: the ninth header include/tdk_hip_highlights.h (highlight reconstruction) -- it parses to exactly its five declarations,
-the library exports them, the ctypes table _native.HIGHLIGHTS_SIGNATURES mirrors it parameter for parameter, header and source are
-part of the build's source hash, every argument error of tdk_highlights and tdk_highlights_chrominance is reported on the host
+"""CPU-only: the ninth header include/tdk_hip_highlights.h (highlight reconstruction) -- it parses to exactly its five declarations
+(exports and the ctypes table: tests/test_header_abi.py), its source is part of the build's source hash,
+every argument error of tdk_highlights and tdk_highlights_chrominance is reported on the host
 before any HIP call, and the Python front-end torch_darktable.Highlights and the pipeline hook raise the error types of the other
 operators."""
 
-import ctypes
 import inspect
 import re
 from pathlib import Path
 
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations, load_build_module
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_highlights.h'
@@ -21,7 +20,9 @@ CLIP, OPPOSED = 0, 1
 RGGB = 0x94949494
 
 
-def test_header_declares_the_highlights_surface():
+def test_header_declares_the_highlights_surface(td):
+    from torch_darktable import _native
+
     decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
@@ -40,36 +41,9 @@ def test_header_declares_the_highlights_surface():
                     'chroma[c] = cnt[c] >= min_count ? (float)((double)sum[c] / ((double)cnt[c] * 1048576.0)) : 0.0f', 'out = fmaxf(v, ref + chroma[c])',
                     'out = fmaxf(v, 0.0f)'):
         assert formula in text, formula
-
-
-def test_library_exports_every_highlights_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_highlights.h but not exported'
-    lib.tdk_highlights_abi_version.restype = ctypes.c_int
-    assert lib.tdk_highlights_abi_version() == 1
-
-
-def test_highlights_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.HIGHLIGHTS_SIGNATURES) == sorted(decls)
-    assert not set(_native.HIGHLIGHTS_SIGNATURES) & signature_tables_except('HIGHLIGHTS_SIGNATURES')
-    for name, (restype, argtypes) in _native.HIGHLIGHTS_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_HL_CLIP, _native.TDK_HL_OPPOSED) == (CLIP, OPPOSED)
     assert _native.ABI_VERSIONS['tdk_highlights_abi_version'] == (1, 'highlights ABI')
-
-
-def test_header_and_source_are_part_of_the_source_hash():
-    build = load_build_module()
-    assert HEADER in build.LATER_HEADERS and HEADER in build._inputs()
-    assert all(h.exists() for h in build.HEADERS + build.LATER_HEADERS)
-    assert (ROOT / 'torch-darktable_amd' / 'csrc' / 'highlights.hip') in build._inputs()
+    assert (ROOT / 'torch-darktable_amd' / 'csrc' / 'highlights.hip') in load_build_module()._inputs()
 
 
 def test_highlights_invalid_arguments_fail_on_the_host(td):

@@ -9,47 +9,18 @@
    silently stale; tests/test_gpu_fusion.py::test_metrics_one_launch_on_many_grids is the run-time side of the same contract.
 2. RCD strips, approximate flavour (csrc/tdk_rcd_stream.h): no IEEE division expansion (v_div_scale / v_div_fmas / v_div_fixup)
    is left in the float16 kernels' inner blocks -- the instruction saving the flavour exists for."""
-import re
-import subprocess
-from pathlib import Path
-
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / 'torch-darktable_amd' / 'csrc'
-HIPCC = '/opt/rocm/bin/hipcc'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
-
-
-def _asm(stem):
-    r = subprocess.run([HIPCC, *FLAGS, str(CSRC / f'{stem}.hip')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout
-
-
-def _kernels(asm, pattern):
-    """{symbol: body lines} of the kernels whose mangled name matches."""
-    out, cur, name = {}, None, None
-    for line in asm.split('\n'):
-        m = re.match(r'^(_Z\w+):', line)
-        if m and re.search(pattern, m.group(1)):
-            name, cur = m.group(1), []
-            continue
-        if cur is not None:
-            cur.append(line.strip())
-            if line.strip().startswith('s_endpgm'):
-                out[name] = cur
-                cur = None
-    return out
+from kernel_isa import device_asm, kernel_bodies
 
 
 @pytest.fixture(scope='module')
 def tonemap_asm():
-    return _asm('tonemap')
+    return device_asm('tonemap')
 
 
 def test_metrics_one_launch_handoff_instructions(tonemap_asm):
-    ks = _kernels(tonemap_asm, r'metrics_kernelI\w+Lb1E')
+    ks = kernel_bodies(tonemap_asm, r'metrics_kernelI\w+Lb1E')
     assert len(ks) == 2, list(ks)  # float and __half storage
     for name, body in ks.items():
         ops = [l.split()[0] for l in body if l and not l.startswith((';', '.'))]
@@ -68,7 +39,7 @@ def test_bounds_one_launch_handoff_instructions(tonemap_asm):
     """tdk_image_bounds (bounds_ticket_kernel): the same fence-less hand-off as the metrics kernel.  Minimum and maximum are single
     integer atomics on order-preserving keys (no compare-and-swap loop on cached data), they have completed (vmcnt(0)) before the
     returning ticket atomic is issued, and the workgroup that draws the last ticket reads the two keys with agent-scope loads."""
-    ks = _kernels(tonemap_asm, r'bounds_ticket_kernelI')
+    ks = kernel_bodies(tonemap_asm, r'bounds_ticket_kernelI')
     assert len(ks) == 2, list(ks)
     for name, body in ks.items():
         ops = [l.split()[0] for l in body if l and not l.startswith((';', '.'))]
@@ -83,8 +54,8 @@ def test_bounds_one_launch_handoff_instructions(tonemap_asm):
 
 
 def test_rcd_approximate_flavour_has_no_ieee_division_in_its_inner_blocks():
-    asm = _asm('rcd')
-    ks = _kernels(asm, r'(rcd_quadILi4E\w+Lb1E|rcd_streamI\w+Lb1E)')
+    asm = device_asm('rcd')
+    ks = kernel_bodies(asm, r'(rcd_quadILi4E\w+Lb1E|rcd_streamI\w+Lb1E)')
     assert len(ks) == 4, list(ks)  # {quad, stream} x {half, float mosaic} with float16 results
     for name, body in ks.items():
         ops = [l.split()[0] for l in body if l and not l.startswith((';', '.'))]

@@ -1,5 +1,5 @@
-"""CPU-only: the third header include/tdk_hip_denoise.h (non-local means) -- it parses, the library exports every declaration, the
-ctypes table _native.DENOISE_SIGNATURES mirrors it parameter for parameter, every argument error of tdk_nlmeans is reported on
+"""CPU-only: the third header include/tdk_hip_denoise.h (non-local means) -- it parses to exactly its three declarations
+(exports and the ctypes table: tests/test_header_abi.py), every argument error of tdk_nlmeans is reported on
 the host before any HIP call, and the Python front-end torch_darktable.NLMeans raises the error types of Wiener."""
 
 import ctypes
@@ -8,44 +8,21 @@ from pathlib import Path
 
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_denoise.h'
 EXPECTED = ['tdk_denoise_abi_version', 'tdk_nlmeans', 'tdk_nlmeans_lds_bytes']
 
 
-def test_header_declares_the_denoise_surface():
+def test_header_declares_the_denoise_surface(td):
+    from torch_darktable import _native
+
     assert sorted(declarations(HEADER)) == EXPECTED
     text = HEADER.read_text()
     assert re.search(r'#define TDK_DENOISE_ABI_VERSION 1\b', text)
     assert '#include "tdk_hip.h"' in text and 'extern "C"' in text
-
-
-def test_library_exports_every_denoise_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_denoise.h but not exported'
-    lib.tdk_denoise_abi_version.restype = ctypes.c_int
-    assert lib.tdk_denoise_abi_version() == 1
-
-
-def test_denoise_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.DENOISE_SIGNATURES) == sorted(decls)
-    assert not set(_native.DENOISE_SIGNATURES) & signature_tables_except('DENOISE_SIGNATURES')
-    for name, (restype, argtypes) in _native.DENOISE_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
-
-
-def test_the_header_is_part_of_the_source_hash():
-    build = load_build_module()
-    assert HEADER in build.HEADERS and HEADER in build._inputs()
+    assert _native.ABI_VERSIONS['tdk_denoise_abi_version'] == (1, 'denoise ABI')
 
 
 def test_nlmeans_invalid_arguments_fail_on_the_host(td):

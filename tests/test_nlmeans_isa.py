@@ -7,31 +7,21 @@ code-object metadata and ISA.
   * the tile is dynamic LDS only, and for every legal (S, P, C) it is at most 80 KB, so at least two workgroups share a CU;
   * the horizontal half of the patch sum is 2P whole-wave DPP adds per output row -- no LDS round trip, no permute."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
+from kernel_isa import device_asm, kernel_bodies, metadata
+
 ROWS = 8   # output rows per lane (NLM_ROWS)
 
 
 @pytest.fixture(scope='module')
 def asm():
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, str(ROOT / 'torch-darktable_amd' / 'csrc' / 'nlmeans.hip')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout
+    return device_asm('nlmeans')
 
 
 def _metadata(asm):
-    """{kernel: {field: value}} from the code-object metadata: one map per kernel, opened by a '  - .' line, fields in any order."""
-    out = {}
-    text = asm[asm.index('amdhsa.kernels:'):asm.index('.end_amdgpu_metadata')]
-    for chunk in re.split(r'\n  - (?=\.)', text)[1:]:
-        fields = dict(re.findall(r'^\s*\.(\w+):\s+(\S+)\s*$', chunk, flags=re.M))
-        out[fields['name']] = {k: int(v) for k, v in fields.items() if v.isdigit()}
-    return {k: v for k, v in out.items() if 'nlmeans' in k}
+    return {k: v for k, v in metadata(asm).items() if 'nlmeans' in k}
 
 
 def test_every_nlmeans_kernel_lives_in_registers_and_lds(asm):
@@ -55,16 +45,7 @@ def test_lds_leaves_room_for_two_workgroups_per_cu(td):
 
 
 def test_horizontal_patch_sum_is_dpp(asm):
-    bodies, name = {}, None
-    for line in asm.split('\n'):
-        m = re.match(r'^(_Z\w*nlmeans_kernel\w+):', line)
-        if m:
-            name = m.group(1)
-            bodies[name] = []
-        elif name:
-            bodies[name].append(line.strip())
-            if line.strip().startswith('s_endpgm'):
-                name = None
+    bodies = kernel_bodies(asm, r'^_Z\w*nlmeans_kernel\w+$')
     assert len(bodies) == 16
     for name, body in bodies.items():
         p = int(re.search(r'Li[13]ELi(\d)E', name).group(1))

@@ -1,5 +1,5 @@
-"""CPU-only: the sixth header include/tdk_hip_raw.h (sensor correction) -- it parses to exactly its three declarations, the library
-exports them, the ctypes table _native.RAW_SIGNATURES mirrors it parameter for parameter, every argument error of tdk_raw_prepare is
+"""CPU-only: the sixth header include/tdk_hip_raw.h (sensor correction) -- it parses to exactly its three declarations
+(exports and the ctypes table: tests/test_header_abi.py), every argument error of tdk_raw_prepare is
 reported on the host before any HIP call and names its argument, the LDS query stays within 64 KB, and the Python front end
 torch_darktable.RawPrepare forms black and scale as the header says and raises the error types of Warp and Resize."""
 
@@ -10,7 +10,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_raw.h'
@@ -20,7 +20,9 @@ PACKED12, PACKED12_IDS, U16, RAW_F32, RAW_F16 = range(5)
 RGGB = 0x94949494
 
 
-def test_header_declares_the_raw_surface():
+def test_header_declares_the_raw_surface(td):
+    from torch_darktable import _native
+
     decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
@@ -38,34 +40,9 @@ def test_header_declares_the_raw_surface():
                     'qx1 = min(qx + 1, gw - 1)', 'g0 = G[qy][qx][p]*(1.0f - ax) + G[qy][qx1][p]*ax', 'g  = g0*(1.0f - ay) + g1*ay',
                     'v = min(max(v*gains[colour], 0.0f), 1.0f)', '4*(gw - 1) <= W - 1'):
         assert formula in text, formula
-
-
-def test_library_exports_every_raw_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_raw.h but not exported'
-    lib.tdk_raw_abi_version.restype = ctypes.c_int
-    assert lib.tdk_raw_abi_version() == 1
-
-
-def test_raw_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.RAW_SIGNATURES) == sorted(decls)
-    assert not set(_native.RAW_SIGNATURES) & signature_tables_except('RAW_SIGNATURES')
-    for name, (restype, argtypes) in _native.RAW_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_RAW_PACKED12, _native.TDK_RAW_PACKED12_IDS, _native.TDK_RAW_U16, _native.TDK_RAW_F32, _native.TDK_RAW_F16) == (0, 1, 2, 3, 4)
     assert (_native.TDK_RAW_HOT, _native.TDK_RAW_DEAD) == (1, 2)
-
-
-def test_the_header_is_part_of_the_source_hash():
-    build = load_build_module()
-    assert HEADER in build.HEADERS and HEADER in build._inputs()
+    assert _native.ABI_VERSIONS['tdk_raw_abi_version'] == (1, 'raw ABI')
 
 
 def test_raw_prepare_invalid_arguments_fail_on_the_host(td):

@@ -1,15 +1,14 @@
-"""CPU-only: the fourth header include/tdk_hip_resample.h (antialiased scaling) -- it parses to exactly its three declarations, the
-library exports them, the ctypes table _native.RESAMPLE_SIGNATURES mirrors it parameter for parameter, every argument error of
+"""CPU-only: the fourth header include/tdk_hip_resample.h (antialiased scaling) -- it parses to exactly its three declarations
+(exports and the ctypes table: tests/test_header_abi.py), every argument error of
 tdk_resample is reported on the host before any HIP call, the LDS query stays within (0, 80 KB], and the Python front-end
 torch_darktable.Resize and the pipeline entry points exist and raise the error types of NLMeans."""
 
-import ctypes
 import re
 from pathlib import Path
 
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_resample.h'
@@ -17,7 +16,9 @@ EXPECTED = ['tdk_resample', 'tdk_resample_abi_version', 'tdk_resample_lds_bytes'
 F32, F16, U8 = 0, 1, 2
 
 
-def test_header_declares_the_resample_surface():
+def test_header_declares_the_resample_surface(td):
+    from torch_darktable import _native
+
     decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
@@ -29,33 +30,8 @@ def test_header_declares_the_resample_surface():
     assert decls['tdk_resample_lds_bytes'] == ('size_t', ['int src_width', 'int src_height', 'int dst_width', 'int dst_height', 'int channels', 'int dtype'])
     for formula in ('s = n_in / n_out', 'r = max(s, 1)', 'c = s (i + 1/2)', 'w_j = max(0, 1 - |j + 1/2 - c| / r)', 'y_i = sum_j w_j x_j / sum_j w_j'):
         assert formula in text, formula
-
-
-def test_library_exports_every_resample_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_resample.h but not exported'
-    lib.tdk_resample_abi_version.restype = ctypes.c_int
-    assert lib.tdk_resample_abi_version() == 1
-
-
-def test_resample_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.RESAMPLE_SIGNATURES) == sorted(decls)
-    assert not set(_native.RESAMPLE_SIGNATURES) & signature_tables_except('RESAMPLE_SIGNATURES')
-    for name, (restype, argtypes) in _native.RESAMPLE_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_F32, _native.TDK_F16, _native.TDK_U8) == (F32, F16, U8)
-
-
-def test_the_header_is_part_of_the_source_hash():
-    build = load_build_module()
-    assert HEADER in build.HEADERS and HEADER in build._inputs()
+    assert _native.ABI_VERSIONS['tdk_resample_abi_version'] == (1, 'resample ABI')
 
 
 def test_resample_invalid_arguments_fail_on_the_host(td):

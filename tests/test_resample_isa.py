@@ -8,31 +8,23 @@ code-object metadata.
   * the tile is dynamic LDS only -- its size is tdk_resample_lds_bytes, held to 80 KB over a sweep of geometries in
     tests/test_resample_abi.py -- and the kernel never raises its dynamic-LDS limit, so no call but the launch is made."""
 import re
-import subprocess
 from pathlib import Path
 
 import pytest
 
+from kernel_isa import device_asm, metadata
+
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'resample.hip'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
 
 
 @pytest.fixture(scope='module')
 def asm():
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, str(SOURCE)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout
+    return device_asm('resample')
 
 
 def _metadata(asm):
-    """{kernel: {field: value}} from the code-object metadata: one map per kernel, opened by a '  - .' line, fields in any order."""
-    out = {}
-    text = asm[asm.index('amdhsa.kernels:'):asm.index('.end_amdgpu_metadata')]
-    for chunk in re.split(r'\n  - (?=\.)', text)[1:]:
-        fields = dict(re.findall(r'^\s*\.(\w+):\s+(\S+)\s*$', chunk, flags=re.M))
-        out[fields['name']] = {k: int(v) for k, v in fields.items() if v.isdigit()}
-    return {k: v for k, v in out.items() if 'resample_kernel' in k}
+    return {k: v for k, v in metadata(asm).items() if 'resample_kernel' in k}
 
 
 def test_every_resample_kernel_lives_in_registers_and_lds(asm):

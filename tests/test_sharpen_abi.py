@@ -1,5 +1,5 @@
-"""CPU-only: the seventh header include/tdk_hip_sharpen.h (unsharp mask) -- it parses to exactly its four declarations, the library
-exports them, the ctypes table _native.SHARPEN_SIGNATURES mirrors it parameter for parameter, every argument error of tdk_sharpen is
+"""CPU-only: the seventh header include/tdk_hip_sharpen.h (unsharp mask) -- it parses to exactly its four declarations
+(exports and the ctypes table: tests/test_header_abi.py), every argument error of tdk_sharpen is
 reported on the host before any HIP call, the LDS query stays within (0, 64 KB] over every legal (channels, dtype, radius, flags),
 and the Python front-end torch_darktable.Sharpen and the pipeline hook exist and raise the error types of Resize."""
 
@@ -9,7 +9,7 @@ from pathlib import Path
 
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_sharpen.h'
@@ -18,7 +18,9 @@ F32, F16, U8 = 0, 1, 2
 LUMA, LIMIT = 1, 2
 
 
-def test_header_declares_the_sharpen_surface():
+def test_header_declares_the_sharpen_surface(td):
+    from torch_darktable import _native
+
     decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
@@ -33,34 +35,8 @@ def test_header_declares_the_sharpen_surface():
     for formula in ('s = (0.2126729f*r + 0.7151522f*g) + 0.0721750f*b', 'h = w[0]*s[0]', 'h = h + w[k]*(s[-k] + s[+k])', 'd  = s - b',
                     "d' = |d| > t ? copysignf(|d| - t, d) : 0", "y[c] = x[c] + amount * d'", 'y[c] = fminf(fmaxf(y[c], lo[c] - o), hi[c] + o)'):
         assert formula in text, formula
-
-
-def test_library_exports_every_sharpen_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_sharpen.h but not exported'
-    lib.tdk_sharpen_abi_version.restype = ctypes.c_int
-    assert lib.tdk_sharpen_abi_version() == 1
-
-
-def test_sharpen_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.SHARPEN_SIGNATURES) == sorted(decls)
-    assert not set(_native.SHARPEN_SIGNATURES) & signature_tables_except('SHARPEN_SIGNATURES')
-    for name, (restype, argtypes) in _native.SHARPEN_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_SHARPEN_LUMA, _native.TDK_SHARPEN_LIMIT, _native.TDK_SHARPEN_MAX_RADIUS) == (LUMA, LIMIT, 12)
-
-
-def test_the_header_is_part_of_the_source_hash():
-    build = load_build_module()
-    assert HEADER in build.HEADERS and HEADER in build._inputs()
-    assert len(build.HEADERS) == 7 and all(h.exists() for h in build.HEADERS)
+    assert _native.ABI_VERSIONS['tdk_sharpen_abi_version'] == (1, 'sharpen ABI')
 
 
 def test_sharpen_invalid_arguments_fail_on_the_host(td):

@@ -7,28 +7,19 @@ code-object metadata alone.
   * the tile is dynamic LDS only -- its size is tdk_sharpen_lds_bytes, held to 64 KB in tests/test_sharpen_abi.py -- and the kernel
     never raises its dynamic-LDS limit, so no call but the launch is made."""
 import re
-import subprocess
 from pathlib import Path
 
 import pytest
 
+import kernel_isa
+
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'sharpen.hip'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
 
 
 @pytest.fixture(scope='module')
 def metadata():
-    """{kernel: {field: value}} from the code-object metadata: one map per kernel, opened by a '  - .' line, fields in any order."""
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, str(SOURCE)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = r.stdout
-    out = {}
-    text = asm[asm.index('amdhsa.kernels:'):asm.index('.end_amdgpu_metadata')]
-    for chunk in re.split(r'\n  - (?=\.)', text)[1:]:
-        fields = dict(re.findall(r'^\s*\.(\w+):\s+(\S+)\s*$', chunk, flags=re.M))
-        out[fields['name']] = {k: int(v) for k, v in fields.items() if v.isdigit()}
-    return out
+    return kernel_isa.metadata(kernel_isa.device_asm('sharpen'))
 
 
 def test_every_sharpen_kernel_lives_in_registers_and_lds(metadata):

@@ -1,5 +1,5 @@
-"""CPU-only: the fifth header include/tdk_hip_warp.h (parametric warp) -- it parses to exactly its four declarations, the library
-exports them, the ctypes table _native.WARP_SIGNATURES mirrors it parameter for parameter, every argument error of tdk_warp is
+"""CPU-only: the fifth header include/tdk_hip_warp.h (parametric warp) -- it parses to exactly its four declarations
+(exports and the ctypes table: tests/test_header_abi.py), every argument error of tdk_warp is
 reported on the host before any HIP call and names its argument, the LDS query stays within 64 KB, and the Python front-end
 torch_darktable.Warp builds the maps the issue describes and raises the error types of Resize."""
 
@@ -10,7 +10,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_warp.h'
@@ -19,7 +19,9 @@ F32, F16, U8 = 0, 1, 2
 IDENTITY = [1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]
 
 
-def test_header_declares_the_warp_surface():
+def test_header_declares_the_warp_surface(td):
+    from torch_darktable import _native
+
     decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
@@ -34,33 +36,8 @@ def test_header_declares_the_warp_surface():
                     'ty = p1*(r2 + (y2 + y2)) + p2*(xy + xy)', 'xd = x*rad + tx', 'sx = fx*xd + cx', 'sx = min(max(sx, -4), sw + 3)',
                     'c1(t) = ((1.25f*t - 2.25f)*t)*t + 1.0f', 'c2(t) = ((-0.75f*t + 3.75f)*t - 6.0f)*t + 3.0f', '((s0*w0 + s1*w1) + s2*w2) + s3*w3'):
         assert formula in text, formula
-
-
-def test_library_exports_every_warp_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_warp.h but not exported'
-    lib.tdk_warp_abi_version.restype = ctypes.c_int
-    assert lib.tdk_warp_abi_version() == 1
-
-
-def test_warp_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.WARP_SIGNATURES) == sorted(decls)
-    assert not set(_native.WARP_SIGNATURES) & signature_tables_except('WARP_SIGNATURES')
-    for name, (restype, argtypes) in _native.WARP_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert _native.TDK_WARP_DIRECT == 1 and _native.TDK_U8 == U8
-
-
-def test_the_header_is_part_of_the_source_hash():
-    build = load_build_module()
-    assert HEADER in build.HEADERS and HEADER in build._inputs()
+    assert _native.ABI_VERSIONS['tdk_warp_abi_version'] == (1, 'warp ABI')
 
 
 def test_warp_invalid_arguments_fail_on_the_host(td):

@@ -7,35 +7,23 @@ metadata -- kernel names and resource fields only.
   * workgroups of 256 threads; the source box is dynamic LDS only -- its size is tdk_warp_lds_bytes, held to 64 KB in
     tests/test_warp_abi.py -- so the kernel never raises its dynamic-LDS limit and no call but the launch is made."""
 import re
-import subprocess
 from pathlib import Path
 
 import pytest
 
+from kernel_isa import device_asm, metadata
+
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'warp.hip'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
 
 
 @pytest.fixture(scope='module')
 def asm():
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, str(SOURCE)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout
-
-
-def _metadata(asm):
-    """{kernel: {field: value}} from the code-object metadata: one map per kernel, opened by a '  - .' line, fields in any order."""
-    out = {}
-    text = asm[asm.index('amdhsa.kernels:'):asm.index('.end_amdgpu_metadata')]
-    for chunk in re.split(r'\n  - (?=\.)', text)[1:]:
-        fields = dict(re.findall(r'^\s*\.(\w+):\s+(\S+)\s*$', chunk, flags=re.M))
-        out[fields['name']] = {k: int(v) for k, v in fields.items() if v.isdigit()}
-    return out
+    return device_asm('warp')
 
 
 def test_every_warp_kernel_lives_in_registers_and_lds(asm):
-    meta = _metadata(asm)
+    meta = metadata(asm)
     warp = {k: v for k, v in meta.items() if 'warp_kernel' in k}
     coords = {k: v for k, v in meta.items() if 'warp_coordinates_kernel' in k}
     assert len(meta) == 13 and len(warp) == 12 and len(coords) == 1, sorted(meta)

@@ -1,5 +1,5 @@
-"""CPU-only: the eighth header include/tdk_hip_wavelet.h (wavelet denoiser) -- it parses to exactly its five declarations, the
-library exports them, the ctypes table _native.WAVELET_SIGNATURES mirrors it parameter for parameter, every argument error of
+"""CPU-only: the eighth header include/tdk_hip_wavelet.h (wavelet denoiser) -- it parses to exactly its five declarations
+(exports and the ctypes table: tests/test_header_abi.py), every argument error of
 tdk_wavelet is reported on the host before any HIP call, the workspace and LDS queries answer 0 for what the call rejects, and the
 Python front-end torch_darktable.Wavelet and the pipeline hook exist and raise the error types of the other operators."""
 
@@ -10,7 +10,7 @@ from pathlib import Path
 
 import pytest
 
-from abi_header import ctype_of, declarations, load_build_module, signature_tables_except
+from abi_header import declarations, load_build_module
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / 'include' / 'tdk_hip_wavelet.h'
@@ -19,7 +19,9 @@ F32, F16, U8 = 0, 1, 2
 YCC = 1
 
 
-def test_header_declares_the_wavelet_surface():
+def test_header_declares_the_wavelet_surface(td):
+    from torch_darktable import _native
+
     decls = declarations(HEADER)
     assert sorted(decls) == EXPECTED
     text = HEADER.read_text()
@@ -35,37 +37,9 @@ def test_header_declares_the_wavelet_surface():
                     'h = (0.0625f*(c_s[-2p] + c_s[+2p]) + 0.25f*(c_s[-p] + c_s[+p])) + 0.375f*c_s[0]', 'd_s = c_s - c_{s+1}',
                     "d'_s = |d_s| > t ? copysignf(|d_s| - t, d_s) : 0", "acc = acc + d'_s", 'y = acc + c_S'):
         assert formula in text, formula
-
-
-def test_library_exports_every_wavelet_symbol(td):
-    lib = ctypes.CDLL(str(ROOT / 'torch-darktable_amd' / 'torch_darktable' / 'libtdk_hip.so'))
-    for name in EXPECTED:
-        assert hasattr(lib, name), f'{name} declared in tdk_hip_wavelet.h but not exported'
-    lib.tdk_wavelet_abi_version.restype = ctypes.c_int
-    assert lib.tdk_wavelet_abi_version() == 1
-
-
-def test_wavelet_ctypes_table_matches_header(td):
-    from torch_darktable import _native
-
-    decls = declarations(HEADER)
-    assert sorted(_native.WAVELET_SIGNATURES) == sorted(decls)
-    assert not set(_native.WAVELET_SIGNATURES) & signature_tables_except('WAVELET_SIGNATURES')
-    for name, (restype, argtypes) in _native.WAVELET_SIGNATURES.items():
-        ret, params = decls[name]
-        assert restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), name
-        assert [ctype_of(p) for p in params] == list(argtypes), f'{name}: header {params}, ctypes {argtypes}'
-        assert getattr(_native.lib, name).argtypes == list(argtypes)
     assert (_native.TDK_WAVELET_YCC, _native.TDK_WAVELET_MAX_SCALES) == (YCC, 5)
     assert _native.ABI_VERSIONS['tdk_wavelet_abi_version'] == (1, 'wavelet ABI')
-
-
-def test_the_header_is_part_of_the_source_hash():
-    build = load_build_module()
-    # (build.HEADERS stays the seven headers tests/test_sharpen_abi.py counts; the later ones are hashed and watched next to them)
-    assert HEADER in build.LATER_HEADERS and HEADER in build._inputs()
-    assert all(h.exists() for h in build.HEADERS + build.LATER_HEADERS)
-    assert (ROOT / 'torch-darktable_amd' / 'csrc' / 'wavelet.hip') in build._inputs()
+    assert (ROOT / 'torch-darktable_amd' / 'csrc' / 'wavelet.hip') in load_build_module()._inputs()
 
 
 def test_wavelet_invalid_arguments_fail_on_the_host(td):

@@ -6,29 +6,20 @@ code-object metadata alone.
   * the planes are static LDS, at most 64 KB, and the largest workgroup of a call is what tdk_wavelet_lds_bytes answers;
   * at most 128 VGPRs, so registers admit four waves per SIMD of the 512-entry file."""
 import re
-import subprocess
 from pathlib import Path
 
 import pytest
 
+import kernel_isa
+
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'wavelet.hip'
-FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fno-slp-vectorize', '--cuda-device-only', '-S', '-o', '-']
 F32, F16, YCC = 0, 1, 1
 
 
 @pytest.fixture(scope='module')
 def metadata():
-    """{kernel: {field: value}} from the code-object metadata: one map per kernel, opened by a '  - .' line, fields in any order."""
-    r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, str(SOURCE)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = r.stdout
-    out = {}
-    text = asm[asm.index('amdhsa.kernels:'):asm.index('.end_amdgpu_metadata')]
-    for chunk in re.split(r'\n  - (?=\.)', text)[1:]:
-        fields = dict(re.findall(r'^\s*\.(\w+):\s+(\S+)\s*$', chunk, flags=re.M))
-        out[fields['name']] = {k: int(v) for k, v in fields.items() if v.isdigit()}
-    return out
+    return kernel_isa.metadata(kernel_isa.device_asm('wavelet'))
 
 
 def kinds(metadata):

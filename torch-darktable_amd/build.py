@@ -36,13 +36,11 @@ CXXFLAGS += os.environ.get('TDK_EXTRA_FLAGS', '').split()  # experiments: e.g. T
 
 
 HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip.h', 'tdk_hip_ext.h', 'tdk_hip_denoise.h', 'tdk_hip_resample.h', 'tdk_hip_warp.h', 'tdk_hip_raw.h',
-                                                       'tdk_hip_sharpen.h')]
-# the headers added after the seven above, whose number tests/test_sharpen_abi.py pins
-LATER_HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip_wavelet.h', 'tdk_hip_highlights.h')]
+                                                       'tdk_hip_sharpen.h', 'tdk_hip_wavelet.h', 'tdk_hip_highlights.h')]
 
 
 def _inputs():
-  return sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + HEADERS + LATER_HEADERS
+  return sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + HEADERS
 
 
 def source_hash() -> str:
@@ -82,7 +80,7 @@ def _stale(target: Path, deps) -> bool:
 
 def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -> Path:
   OBJ.mkdir(exist_ok=True)
-  headers = list(CSRC.glob('*.h')) + HEADERS + LATER_HEADERS
+  headers = list(CSRC.glob('*.h')) + HEADERS
   sources = sorted(CSRC.glob('*.hip'))
   todo = []
   objs = []

@@ -159,21 +159,21 @@ HIGHLIGHTS_SIGNATURES = {
   'tdk_highlights': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
 }
 
-ALL_SIGNATURES = (SIGNATURES, EXT_SIGNATURES, DENOISE_SIGNATURES, RESAMPLE_SIGNATURES, WARP_SIGNATURES, RAW_SIGNATURES, SHARPEN_SIGNATURES,
-                  WAVELET_SIGNATURES, HIGHLIGHTS_SIGNATURES)
-
-# the version function of each header -> (the version this package was written against, its name in the ImportError)
-ABI_VERSIONS = {
-  'tdk_abi_version': (4, 'ABI'),
-  'tdk_ext_abi_version': (1, 'extension ABI'),
-  'tdk_denoise_abi_version': (1, 'denoise ABI'),
-  'tdk_resample_abi_version': (1, 'resample ABI'),
-  'tdk_warp_abi_version': (1, 'warp ABI'),
-  'tdk_raw_abi_version': (1, 'raw ABI'),
-  'tdk_sharpen_abi_version': (1, 'sharpen ABI'),
-  'tdk_wavelet_abi_version': (1, 'wavelet ABI'),
-  'tdk_highlights_abi_version': (1, 'highlights ABI'),
-}
+# one row per public header, in the order of build.HEADERS:
+# (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
+HEADERS = (
+  ('tdk_hip.h', SIGNATURES, 'tdk_abi_version', 4, 'ABI'),
+  ('tdk_hip_ext.h', EXT_SIGNATURES, 'tdk_ext_abi_version', 1, 'extension ABI'),
+  ('tdk_hip_denoise.h', DENOISE_SIGNATURES, 'tdk_denoise_abi_version', 1, 'denoise ABI'),
+  ('tdk_hip_resample.h', RESAMPLE_SIGNATURES, 'tdk_resample_abi_version', 1, 'resample ABI'),
+  ('tdk_hip_warp.h', WARP_SIGNATURES, 'tdk_warp_abi_version', 1, 'warp ABI'),
+  ('tdk_hip_raw.h', RAW_SIGNATURES, 'tdk_raw_abi_version', 1, 'raw ABI'),
+  ('tdk_hip_sharpen.h', SHARPEN_SIGNATURES, 'tdk_sharpen_abi_version', 1, 'sharpen ABI'),
+  ('tdk_hip_wavelet.h', WAVELET_SIGNATURES, 'tdk_wavelet_abi_version', 1, 'wavelet ABI'),
+  ('tdk_hip_highlights.h', HIGHLIGHTS_SIGNATURES, 'tdk_highlights_abi_version', 1, 'highlights ABI'),
+)
+ALL_SIGNATURES = tuple(table for _, table, _, _, _ in HEADERS)
+ABI_VERSIONS = {version_fn: (expected, label) for _, _, version_fn, expected, label in HEADERS}
 
 TDK_F32, TDK_F16 = 0, 1
 TDK_U8 = 2  # include/tdk_hip_resample.h: taken by tdk_resample and tdk_warp only

@@ -16,6 +16,7 @@ from __future__ import annotations
 import torch
 
 from ._native import lib
+from ._streams import StreamBuffers
 from .jpeg import InputFormat, JpegException, Subsampling
 from .torch_darktable_extension import JpegInputFormat, JpegSubsampling, _ptr, _require, _stream
 
@@ -68,7 +69,7 @@ class DeviceJpeg:
     serve several streams (one workspace each) and the calls of one stream reuse theirs."""
 
     def __init__(self):
-        self._workspaces = {}
+        self._workspaces = StreamBuffers()
 
     @staticmethod
     def max_stream_bytes(width: int, height: int, subsampling=Subsampling.CSS_422, progressive: bool = False) -> int:
@@ -101,10 +102,7 @@ class DeviceJpeg:
             if nbytes == 0:
                 raise JpegException(f'nvjpegEncodeImage, image {w}x{h} not supported')
             stream = torch.cuda.current_stream(image.device)
-            key = (w, h, int(sub), image.device, stream.cuda_stream)
-            ws = self._workspaces.get(key)
-            if ws is None:
-                ws = self._workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
+            ws = self._workspaces.get(nbytes, image.device, key=(w, h, int(sub), image.device))
             if out is None:
                 out = torch.empty(self.max_stream_bytes(w, h, sub, progressive), dtype=torch.uint8, device=image.device)
             length = torch.empty((), dtype=torch.int64, device=image.device)

@@ -28,11 +28,12 @@ import math
 
 import torch
 
+from ._frames import MAX_SIZE, require_cuda_device
 from ._native import TDK_F16, TDK_F32, TDK_HL_CLIP, TDK_HL_OPPOSED, check, lib
+from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-MAX_SIZE = 65535
 MAX_GAIN = 64.0
 _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _MODES = {'clip': TDK_HL_CLIP, 'opposed': TDK_HL_OPPOSED}
@@ -45,8 +46,7 @@ class Highlights:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, mode: str = 'opposed',
                  threshold: float = 0.98, low: float = 0.2, min_count: int = 64):
-        if device.type != 'cuda':
-            raise ValueError(f'Device must be CUDA, got {device}')
+        require_cuda_device(device)
         width, height = (int(v) for v in image_size)
         if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
             raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
@@ -66,7 +66,8 @@ class Highlights:
         self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
         self.mode = mode
         self.threshold, self.low, self.min_count = float(threshold), float(low), int(min_count)
-        self._workspaces: dict[int, torch.Tensor] = {}
+        self._workspace_bytes = self.workspace_bytes()
+        self._workspaces = StreamBuffers()
         if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
             self._workspace(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
 
@@ -90,11 +91,7 @@ class Highlights:
         """The records of the statistics launch, one buffer per stream: the object may be used from several streams at once.  The
         buffer of the stream current at construction exists from then on, so a capture allocates nothing.  Every record is written by
         every call that reads them: the buffer is never cleared."""
-        key = torch.cuda.current_stream(device).cuda_stream
-        buf = self._workspaces.get(key)
-        if buf is None:
-            buf = self._workspaces[key] = torch.empty(self.workspace_bytes(), dtype=torch.uint8, device=device)
-        return buf
+        return self._workspaces.get(self._workspace_bytes, device)
 
     def _check_mosaic(self, mosaic: torch.Tensor) -> int:
         assert mosaic.dim() == 2, f'mosaic must have 2 dimensions, got {mosaic.shape}'

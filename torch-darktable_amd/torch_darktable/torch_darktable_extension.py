@@ -29,6 +29,7 @@ import torch
 
 from . import _native
 from ._native import TDK_F16, TDK_F32, check, lib
+from ._streams import StreamBuffers
 
 __all__ = [
   'BayerPattern', 'PPG', 'RCD', 'PostProcess', 'Laplacian', 'Bilateral', 'Wiener', 'TonemapParams',
@@ -216,6 +217,7 @@ class _Workspace:
     self._device = device
     self._width = int(width)
     self._height = int(height)
+    self._scratch = StreamBuffers()
 
   @property
   def width(self) -> int:
@@ -231,15 +233,10 @@ class _Workspace:
   def _workspace(self, nbytes: int, device: torch.device) -> torch.Tensor:
     """Cached scratch of at least `nbytes`, one buffer per CUDA stream: a workspace object may be used from
     several streams (or threads with different current streams) without its kernels sharing slabs / grids."""
-    cache = self.__dict__.setdefault('_scratch', {})
-    key = torch.cuda.current_stream(device).cuda_stream
-    buf = cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-      buf = cache[key] = _workspace(max(int(nbytes), 256), device)
-    return buf
+    return self._scratch.get(max(int(nbytes), 256), device)
 
   def _drop_workspaces(self) -> None:
-    self.__dict__.pop('_scratch', None)
+    self._scratch.clear()
 
 
 class PPG(_Workspace):

@@ -22,6 +22,7 @@ import torch
 
 from ._frames import TAGS, check_frame, check_size, require_cuda_device
 from ._native import TDK_WAVELET_MAX_SCALES, TDK_WAVELET_YCC, check, lib
+from ._streams import StreamBuffers
 from .extension import extension
 from .torch_darktable_extension import _ptr, _stream
 
@@ -59,7 +60,7 @@ class Wavelet:
         if self.ycc and self.channels == 1:
             raise ValueError('ycc needs three channels, the thresholds have one per scale')
         self._c_thresholds: dict[int, ctypes.Array] = {}
-        self._workspaces: dict[int, torch.Tensor] = {}
+        self._workspaces = StreamBuffers()
         if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
             self._workspace(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
 
@@ -129,13 +130,7 @@ class Wavelet:
         """The float32 planes between the launches, one buffer per stream (sized for three channels): the object may be used from
         several streams at once.  The buffer of the stream current at construction exists from then on, so a capture allocates nothing."""
         nbytes = self.workspace_bytes(3)
-        if nbytes == 0:
-            return None
-        key = torch.cuda.current_stream(device).cuda_stream
-        buf = self._workspaces.get(key)
-        if buf is None:
-            buf = self._workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return buf
+        return self._workspaces.get(nbytes, device) if nbytes else None
 
     def _threshold_array(self, channels: int) -> ctypes.Array:
         arr = self._c_thresholds.get(channels)
