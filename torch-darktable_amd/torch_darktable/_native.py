@@ -159,6 +159,14 @@ HIGHLIGHTS_SIGNATURES = {
   'tdk_highlights': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_lut.h, the colour transform (matrix, lut_lo, lut_scale: host pointers; shaper, lut: device pointers)
+LUT_SIGNATURES = {
+  'tdk_lut_abi_version': (c_int, []),
+  'tdk_color_lut': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p,
+                            c_int, c_int, c_void_p]),
+  'tdk_lut_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -171,6 +179,7 @@ HEADERS = (
   ('tdk_hip_sharpen.h', SHARPEN_SIGNATURES, 'tdk_sharpen_abi_version', 1, 'sharpen ABI'),
   ('tdk_hip_wavelet.h', WAVELET_SIGNATURES, 'tdk_wavelet_abi_version', 1, 'wavelet ABI'),
   ('tdk_hip_highlights.h', HIGHLIGHTS_SIGNATURES, 'tdk_highlights_abi_version', 1, 'highlights ABI'),
+  ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
 )
 ALL_SIGNATURES = tuple(table for _, table, _, _, _ in HEADERS)
 ABI_VERSIONS = {version_fn: (expected, label) for _, _, version_fn, expected, label in HEADERS}
@@ -186,6 +195,9 @@ TDK_SHARPEN_MAX_RADIUS = 12
 TDK_WAVELET_YCC = 1  # include/tdk_hip_wavelet.h: flags of tdk_wavelet
 TDK_WAVELET_MAX_SCALES = 5
 TDK_HL_CLIP, TDK_HL_OPPOSED = 0, 1  # include/tdk_hip_highlights.h: mode of tdk_highlights
+TDK_LUT_TETRAHEDRAL, TDK_LUT_TRILINEAR = 0, 1  # include/tdk_hip_lut.h: interp of tdk_color_lut
+TDK_LUT_GLOBAL = 1  # ... and its flag
+TDK_LUT_MAX_SHAPER, TDK_LUT_MAX_SIZE = 1024, 65
 
 
 def load() -> C.CDLL:

@@ -1,6 +1,6 @@
 """packed raw bytes -> uint8 RGB: decode -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
-[wavelet chroma denoise] ->
-normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [sharpen] -> orientation
+[wavelet chroma denoise] -> [colour transform] ->
+normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  `process_resized` / `process_image_set_resized` put the
 antialiased scaler to `final_size` between the tone mapper and the sharpener; `process` / `process_image_set` ignore
 `resize_width`, as the reference does.
@@ -16,6 +16,7 @@ import torch
 from .. import debayer as _debayer
 from .. import tonemap as _tonemap
 from ..bayer import BayerPattern, PackedFormat
+from ..colorlut import ColorLUT
 from ..denoise import Wiener
 from ..highlights import Highlights
 from ..local_contrast import Bilateral
@@ -44,7 +45,8 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, highlights: Highlights | None = None, sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
+                 storage_dtype: torch.dtype = torch.float32, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
+                 sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
         self.device = device
@@ -81,12 +83,19 @@ class ImageProcessor:
         # reference's chain
         if highlights is not None:
             if not isinstance(highlights, Highlights):
-                raise TypeError(f'highlights must be a Highlights or None, got {type(highlights).__name__} (sharpen is the argument after it: pass both by keyword)')
+                raise TypeError(f'highlights must be a Highlights or None, got {type(highlights).__name__} (color is the argument after it: pass both by keyword)')
             if highlights.image_size != tuple(image_size) or highlights.bayer_pattern != bayer_pattern:
                 raise ValueError(f'highlights is for {highlights.image_size} {highlights.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
             if white_balance is None:
                 raise ValueError('highlights needs white_balance: it applies the gains itself')
         self.highlights = highlights
+        # colour management: `color` is the input transform (camera matrix, curves) on every demosaiced frame, behind the chroma
+        # denoiser and in front of the bounds, storage type in and out; `look` grades the tone-mapped uint8 frame in front of the
+        # scaler; None: the reference's chain
+        for name, stage in (('color', color), ('look', look)):
+            if stage is not None and not isinstance(stage, ColorLUT):
+                raise TypeError(f'{name} must be a ColorLUT or None, got {type(stage).__name__} (pass the arguments behind highlights by keyword)')
+        self.color, self.look = color, look
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -298,6 +307,8 @@ class ImageProcessor:
         rgb = [self.load_image(b) for b in image_set_bytes.values()]
         if self.chroma_denoise is not None:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
+        if self.color is not None:
+            rgb = [self.color.process(img) for img in rgb]
         bounds = _tonemap.compute_image_bounds(rgb, stride=8)
         self.bounds = lerp(self.bounds if self.bounds is not None else bounds, bounds, ema)
         acc = _tonemap.MetricsAccumulator(self.device, stride=8)  # == compute_image_metrics(rgb, stride=8), fed by the last stage
@@ -305,6 +316,8 @@ class ImageProcessor:
         metrics = acc.finish()
         self.metrics = lerp(self.metrics if self.metrics is not None else metrics, metrics, ema)
         mapped = [self.tonemap(img, self.metrics) for img in rgb]
+        if self.look is not None:
+            mapped = [self.look.process(img) for img in mapped]
         if resized and self.resize_workspace is not None:
             mapped = [self.resize_workspace.process(img) for img in mapped]
         if self.sharpen is not None:
