@@ -159,6 +159,15 @@ HIGHLIGHTS_SIGNATURES = {
   'tdk_highlights': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_stats.h, the frame statistics (frames, quantiles: host pointers; counts, values: device pointers)
+STATS_SIGNATURES = {
+  'tdk_framestats_abi_version': (c_int, []),
+  'tdk_framestats_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_framestats_lds_bytes': (c_size_t, [c_int, c_int]),
+  'tdk_framestats': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_uint32, c_int, c_int, c_float, c_float, c_int, c_void_p, c_int, c_void_p,
+                             c_void_p, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_lut.h, the colour transform (matrix, lut_lo, lut_scale: host pointers; shaper, lut: device pointers)
 LUT_SIGNATURES = {
   'tdk_lut_abi_version': (c_int, []),
@@ -179,6 +188,7 @@ HEADERS = (
   ('tdk_hip_sharpen.h', SHARPEN_SIGNATURES, 'tdk_sharpen_abi_version', 1, 'sharpen ABI'),
   ('tdk_hip_wavelet.h', WAVELET_SIGNATURES, 'tdk_wavelet_abi_version', 1, 'wavelet ABI'),
   ('tdk_hip_highlights.h', HIGHLIGHTS_SIGNATURES, 'tdk_highlights_abi_version', 1, 'highlights ABI'),
+  ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
 )
 ALL_SIGNATURES = tuple(table for _, table, _, _, _ in HEADERS)
@@ -198,6 +208,9 @@ TDK_HL_CLIP, TDK_HL_OPPOSED = 0, 1  # include/tdk_hip_highlights.h: mode of tdk_
 TDK_LUT_TETRAHEDRAL, TDK_LUT_TRILINEAR = 0, 1  # include/tdk_hip_lut.h: interp of tdk_color_lut
 TDK_LUT_GLOBAL = 1  # ... and its flag
 TDK_LUT_MAX_SHAPER, TDK_LUT_MAX_SIZE = 1024, 65
+TDK_U16 = 3  # include/tdk_hip_stats.h: taken by tdk_framestats only
+TDK_STATS_MAX_BINS, TDK_STATS_MAX_FRAMES, TDK_STATS_MAX_QUANTILES = 1024, 16, 8
+TDK_STATS_GRID, TDK_STATS_CHUNK = 512, 8192  # workgroups of the gather launch, pixels of a workgroup per step
 
 
 def load() -> C.CDLL:

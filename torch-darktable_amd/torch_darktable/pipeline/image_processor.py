@@ -1,7 +1,8 @@
 """packed raw bytes -> uint8 RGB: decode -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
 [wavelet chroma denoise] -> [colour transform] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
-(reference torch_darktable/pipeline/image_processor.py).  `process_resized` / `process_image_set_resized` put the
+(reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
+instead of the minimum and maximum over the set.  `process_resized` / `process_image_set_resized` put the
 antialiased scaler to `final_size` between the tone mapper and the sharpener; `process` / `process_image_set` ignore
 `resize_width`, as the reference does.
 
@@ -18,6 +19,7 @@ from .. import tonemap as _tonemap
 from ..bayer import BayerPattern, PackedFormat
 from ..colorlut import ColorLUT
 from ..denoise import Wiener
+from ..framestats import FrameStats
 from ..highlights import Highlights
 from ..local_contrast import Bilateral
 from ..rawprepare import RawPrepare
@@ -45,7 +47,7 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
+                 storage_dtype: torch.dtype = torch.float32, exposure: FrameStats | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
                  sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
@@ -96,6 +98,18 @@ class ImageProcessor:
             if stage is not None and not isinstance(stage, ColorLUT):
                 raise TypeError(f'{name} must be a ColorLUT or None, got {type(stage).__name__} (pass the arguments behind highlights by keyword)')
         self.color, self.look = color, look
+        # percentile bounds in the place of the minimum and maximum over the set: a FrameStats on the demosaiced frames, whose first
+        # and last pooled quantile normalise them; None: the reference's chain
+        if exposure is not None:
+            if not isinstance(exposure, FrameStats):
+                raise TypeError(f'exposure must be a FrameStats or None, got {type(exposure).__name__} (pass the arguments behind storage_dtype by keyword)')
+            if exposure.image_size != tuple(image_size):
+                raise ValueError(f'exposure is for {exposure.width}x{exposure.height}, the processor for {image_size[0]}x{image_size[1]}')
+            if exposure.bayer_pattern is not None or exposure.channels != 3:
+                raise ValueError('exposure measures the demosaiced frames: it needs channels=3 and no bayer_pattern')
+            if not exposure.quantiles:
+                raise ValueError('exposure needs at least one quantile: the bounds are its first and last')
+        self.exposure = exposure
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -309,7 +323,9 @@ class ImageProcessor:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
         if self.color is not None:
             rgb = [self.color.process(img) for img in rgb]
-        bounds = _tonemap.compute_image_bounds(rgb, stride=8)
+        if self.exposure is not None and len(rgb) > self.exposure.max_frames:
+            raise ValueError(f'exposure takes {self.exposure.max_frames} frames per call (max_frames), the image set has {len(rgb)}')
+        bounds = self.exposure.bounds(rgb) if self.exposure is not None else _tonemap.compute_image_bounds(rgb, stride=8)
         self.bounds = lerp(self.bounds if self.bounds is not None else bounds, bounds, ema)
         acc = _tonemap.MetricsAccumulator(self.device, stride=8)  # == compute_image_metrics(rgb, stride=8), fed by the last stage
         rgb = [self.process_rgb(img, self.bounds, acc) for img in rgb]
