@@ -168,6 +168,17 @@ STATS_SIGNATURES = {
                              c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_noise.h, the noise profile (frames: a host pointer; counts, model, curve, gains: device pointers)
+NOISE_SIGNATURES = {
+  'tdk_noise_abi_version': (c_int, []),
+  'tdk_noise_workspace_bytes': (c_size_t, [c_int]),
+  'tdk_noise_lds_bytes': (c_size_t, [c_int]),
+  'tdk_noise_profile': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_uint32, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+  'tdk_noise_stabilize': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_uint32, c_void_p, c_void_p, c_float, c_void_p]),
+  'tdk_noise_unstabilize': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_uint32, c_void_p, c_void_p, c_float, c_int, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_lut.h, the colour transform (matrix, lut_lo, lut_scale: host pointers; shaper, lut: device pointers)
 LUT_SIGNATURES = {
   'tdk_lut_abi_version': (c_int, []),
@@ -189,6 +200,7 @@ HEADERS = (
   ('tdk_hip_wavelet.h', WAVELET_SIGNATURES, 'tdk_wavelet_abi_version', 1, 'wavelet ABI'),
   ('tdk_hip_highlights.h', HIGHLIGHTS_SIGNATURES, 'tdk_highlights_abi_version', 1, 'highlights ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
+  ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
 )
 ALL_SIGNATURES = tuple(table for _, table, _, _, _ in HEADERS)
@@ -211,6 +223,11 @@ TDK_LUT_MAX_SHAPER, TDK_LUT_MAX_SIZE = 1024, 65
 TDK_U16 = 3  # include/tdk_hip_stats.h: taken by tdk_framestats only
 TDK_STATS_MAX_BINS, TDK_STATS_MAX_FRAMES, TDK_STATS_MAX_QUANTILES = 1024, 16, 8
 TDK_STATS_GRID, TDK_STATS_CHUNK = 512, 8192  # workgroups of the gather launch, pixels of a workgroup per step
+# include/tdk_hip_noise.h: limits of tdk_noise_profile, the workgroups of its gather launch and the bytes of a row they take per step
+TDK_NOISE_MAX_BINS, TDK_NOISE_MAX_FRAMES, TDK_NOISE_LEVELS = 32, 16, 128
+TDK_NOISE_GRID, TDK_NOISE_STRIP_BYTES = 512, 512
+TDK_NOISE_MEDIAN_FACTOR = 0.9796
+TDK_NOISE_ALGEBRAIC, TDK_NOISE_UNBIASED = 0, 1  # inverse of tdk_noise_unstabilize
 
 
 def load() -> C.CDLL:

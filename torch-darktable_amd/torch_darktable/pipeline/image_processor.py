@@ -1,5 +1,5 @@
 """packed raw bytes -> uint8 RGB: decode -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
-[wavelet chroma denoise] -> [colour transform] ->
+[wavelet chroma denoise, with `noise_model` inside the variance-stabilising transform] -> [colour transform] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
 instead of the minimum and maximum over the set.  `process_resized` / `process_image_set_resized` put the
@@ -22,6 +22,7 @@ from ..denoise import Wiener
 from ..framestats import FrameStats
 from ..highlights import Highlights
 from ..local_contrast import Bilateral
+from ..noiseprofile import NoiseModel
 from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
@@ -47,7 +48,7 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, exposure: FrameStats | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
+                 storage_dtype: torch.dtype = torch.float32, exposure: FrameStats | None = None, noise_model: NoiseModel | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
                  sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
@@ -81,6 +82,15 @@ class ImageProcessor:
             if chroma_denoise.channels == 1:
                 raise ValueError('chroma_denoise has thresholds for one channel, the demosaiced frames have three channels')
         self.chroma_denoise = chroma_denoise
+        # the measured noise model of the sensor: chroma_denoise then runs between stabilize and unstabilize, where the noise of every
+        # channel has one level (build the stage with Wavelet.from_sigma(..., sigma=(s, s, s)), s the sigma_out = 1 of the transform);
+        # None: the stage runs on the frame as it is
+        if noise_model is not None:
+            if not isinstance(noise_model, NoiseModel):
+                raise TypeError(f'noise_model must be a NoiseModel or None, got {type(noise_model).__name__} (pass the arguments behind storage_dtype by keyword)')
+            if chroma_denoise is None:
+                raise ValueError('noise_model needs chroma_denoise: it is the stage the transform goes around')
+        self.noise_model = noise_model
         # white balance that reconstructs clipped highlights, in the place of the white balance in front of the demosaic; None: the
         # reference's chain
         if highlights is not None:
@@ -319,7 +329,10 @@ class ImageProcessor:
         names = list(image_set_bytes.keys())
         ema = self.settings.moving_average
         rgb = [self.load_image(b) for b in image_set_bytes.values()]
-        if self.chroma_denoise is not None:
+        if self.chroma_denoise is not None and self.noise_model is not None:
+            m, wb = self.noise_model, self.white_balance
+            rgb = [m.unstabilize(self.chroma_denoise.process(m.stabilize(img, gains=wb)), gains=wb, out_dtype=img.dtype) for img in rgb]
+        elif self.chroma_denoise is not None:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
         if self.color is not None:
             rgb = [self.color.process(img) for img in rgb]
