@@ -20,12 +20,27 @@ __device__ __forceinline__ float tdk_pow(float x, float y) {
   const float r = __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
   return (y == 0.0f) ? 1.0f : r;
 }
+// powf's result for EVERY base: exp2(y * log2 |x|), and for x < 0 what C defines -- the value with the sign of x^y when y is an
+// integer (pow(-2, 1) == -2, pow(-2, 2) == 4), NaN otherwise (|x|^y for x = -inf).  tdk_pow alone turns every negative base into NaN, which a clip then
+// drops to 0 where the reference has a number: modify_hsl with an adjustment of 0 (y == 1) on a pixel whose saturation or lightness
+// is negative (a channel above 1 or below 0).  `y` is a kernel argument at every call site, so the integer test is wave-uniform.
+__device__ __forceinline__ float tdk_pow_signed(float x, float y) {
+  const float r = tdk_pow(fabsf(x), y);
+  if (!(x < 0.0f)) return r;  // also NaN
+  if (y != truncf(y)) return __builtin_isinf(x) ? r : __builtin_nanf("");  // pow(-inf, y) is +inf (y > 0) or +0, not NaN
+  return (fabsf(y) < 16777216.0f && ((int)y & 1)) ? -r : r;
+}
 __device__ __forceinline__ float tdk_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 __device__ __forceinline__ float tdk_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
 __device__ __forceinline__ float tdk_cbrt(float x) { return __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 3.0f)); }
 // a / b as a * rcp(b) (v_rcp_f32, 1 ulp) -- the reference's fast-math division class; the IEEE
 // sequence is ~10 instructions and the colour kernels carry ~18 divisions per pixel.
 __device__ __forceinline__ float tdk_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+// The same quotient for a denominator of ANY size: v_rcp_f32 flushes a denormal result, so a * rcp(b) is 0 for |b| > 2^126 where
+// the quotient is an ordinary number (FLT_MAX / (adapt + FLT_MAX) == 1).  Both operands are scaled by 2^-8 first, which changes no
+// bit of the result while a * 2^-8 is a normal number.
+#define TDK_DIV_WIDE_SCALE 0.00390625f
+__device__ __forceinline__ float tdk_div_wide(float a, float b) { return (a * TDK_DIV_WIDE_SCALE) * __builtin_amdgcn_rcpf(b * TDK_DIV_WIDE_SCALE); }
 __device__ __forceinline__ float tdk_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 
 __device__ __forceinline__ f3 clip3(f3 a) { return mk3(clip01(a.x), clip01(a.y), clip01(a.z)); }
@@ -109,10 +124,11 @@ __device__ __forceinline__ f3 rgb_to_hsl(f3 c) {
   float h = 0.0f, s = 0.0f;
   const float l = (mx + mn) * 0.5f;
   if (delta > 1e-6f) {
-    s = (l < 0.5f) ? tdk_div(delta, mx + mn) : tdk_div(delta, 2.0f - mx - mn);
-    if (mx == c.x) h = tdk_div(c.y - c.z, delta) + (c.y < c.z ? 6.0f : 0.0f);
-    else if (mx == c.y) h = tdk_div(c.z - c.x, delta) + 2.0f;
-    else h = tdk_div(c.x - c.y, delta) + 4.0f;
+    // tdk_div_wide: delta and 2 - mx - mn reach FLT_MAX with the pixel (the same bits as tdk_div for every ordinary pixel)
+    s = (l < 0.5f) ? tdk_div_wide(delta, mx + mn) : tdk_div_wide(delta, 2.0f - mx - mn);
+    if (mx == c.x) h = tdk_div_wide(c.y - c.z, delta) + (c.y < c.z ? 6.0f : 0.0f);
+    else if (mx == c.y) h = tdk_div_wide(c.z - c.x, delta) + 2.0f;
+    else h = tdk_div_wide(c.x - c.y, delta) + 4.0f;
     h *= (1.0f / 6.0f);
   }
   return mk3(h, s, l);
@@ -137,8 +153,8 @@ __device__ __forceinline__ f3 modify_hsl(f3 rgb, float hue, float sat, float lum
   float nh = hsl.x + hue;
   if (nh < 0.0f) nh += 1.0f;
   if (nh > 1.0f) nh -= 1.0f;
-  const float ns = tdk_pow(hsl.y, tdk_div(1.0f, 1.0f + sat));
-  const float nl = tdk_pow(hsl.z, tdk_div(1.0f, 1.0f + lum));
+  const float ns = tdk_pow_signed(hsl.y, tdk_div(1.0f, 1.0f + sat));
+  const float nl = tdk_pow_signed(hsl.z, tdk_div(1.0f, 1.0f + lum));
   return clip3(hsl_to_rgb(mk3(nh, ns, nl)));
 }
 __device__ __forceinline__ f3 vibrance(f3 rgb, float amount) {

@@ -255,15 +255,23 @@ __device__ __forceinline__ float map_key_of(float log_mean) {
   return 0.3f + 0.7f * tdk_pow(normalized, 1.4f);
 }
 // aces.cu:13-34
-__device__ __forceinline__ float rrt_odt(float v) {
+template <bool EXACT> __device__ __forceinline__ float rrt_odt(float v) {
   const float a = v * (v + 0.0245786f) - 0.000090537f;
   const float b = v * (0.983729f * v + 0.4329510f) + 0.238081f;
-  return tdk_div(a, b);
+  return EXACT ? tdk_div_wide(a, b) : tdk_div(a, b);
 }
-__device__ __forceinline__ f3 aces_fit(f3 c) {
+#define TDK_LAB_OVERFLOW 1.197e16f  // from here on ((g + 0.055) / 1.055)^2.4 is infinite in float32
+// 2^60: a LEAN group whose samples stay below it is computed with plain a * rcp(b).  With |c| < 2^60 the Reinhard denominator
+// ad + c stays below 2^61 and the ACES denominator ~v^2 below 2^126 while aces_scale = 2^intensity <= 8 (intensity <= 3 stops); a
+// larger exposure, or an adaptive-ACES input c / ad beyond 2^63 (an adaptation below 1e-19 of the sample), still meets the flush
+// of v_rcp_f32 described at tdk_div_wide.  tdk_div_wide itself is bit-identical to a * rcp(b) only while a * 2^-8 and
+// rcp(b * 2^-8) are normal numbers: for |b| < 2^-118 (an adaptation that small: map_key == 1 with a mean within 1e-35 of 0) it
+// returns inf where a * rcp(b) is still finite -- both far beyond the clip.
+#define TDK_TONEMAP_ORDINARY 1.152921504606846976e18f
+template <bool EXACT> __device__ __forceinline__ f3 aces_fit(f3 c) {
   const f3 a = mk3(0.59719f * c.x + 0.35458f * c.y + 0.04823f * c.z, 0.07600f * c.x + 0.90834f * c.y + 0.01566f * c.z,
                    0.02840f * c.x + 0.13383f * c.y + 0.83777f * c.z);
-  const f3 r = mk3(rrt_odt(a.x), rrt_odt(a.y), rrt_odt(a.z));
+  const f3 r = mk3(rrt_odt<EXACT>(a.x), rrt_odt<EXACT>(a.y), rrt_odt<EXACT>(a.z));
   return mk3(1.60475f * r.x + -0.53108f * r.y + -0.07367f * r.z, -0.10208f * r.x + 1.10813f * r.y + -0.00605f * r.z,
              -0.00327f * r.x + -0.07276f * r.y + 1.07602f * r.z);
 }
@@ -280,21 +288,32 @@ __device__ __forceinline__ float pow_nz(float x, float y) { return __builtin_amd
 
 struct TmConst {
   float key, inv_exposure, m0, m1, m2, inv_gamma, vibrance, light_adapt, aces_scale;
+  bool key_is_one;  // map_key on its upper clamp (a frame at or below min_gray: log_mean <= -9.21034): powf(x, 1) is x, also for x < 0
+  bool mean_may_be_negative;  // ... without a negative sample: a negative metric, or light_adapt outside [0, 1]
 };
 
 // LEAN: vibrance == 0 and 1 / gamma != 0 (both wave-uniform kernel arguments; the launcher picks the instantiation): no Lab
 // round trip in the code at all -- its registers would otherwise set the occupancy of the common path -- and pow_nz
-template <int MODE, bool LEAN> __device__ __forceinline__ f3 tonemap_px(f3 c, const TmConst& k) {
+// EXACT: the arithmetic that also holds for a pixel or a frame far outside any image -- tdk_div_wide, powf's x^1 = x for a negative
+// mean when map_key sits on its upper clamp, the overflow of the skipped round trip.  !EXACT (the LEAN vector body only) leaves those
+// out and, for the linear mapper, reports in `gmax` the largest gamma-encoded channel; the caller runs the EXACT form on the groups
+// that need it.  The other three mappers are bounded (Reinhard's c / (ad + c) by 2^25 even where the sum cancels to its last bit,
+// the ACES fit by 2.3), so with 1 / gamma <= 2 their g never reaches the overflow: the launcher gives them the LEAN form only then.
+template <int MODE, bool LEAN, bool EXACT = true> __device__ __forceinline__ f3 tonemap_px(f3 c, const TmConst& k, float* gmax = nullptr) {
+  auto dv = [](float a, float b) { return EXACT ? tdk_div_wide(a, b) : tdk_div(a, b); };
   auto pw = [](float x, float y) { return LEAN ? pow_nz(x, y) : tdk_pow(x, y); };
   f3 tm;
   if constexpr (MODE == TDK_TONEMAP_ACES) {
-    tm = aces_fit(mk3(c.x * k.aces_scale, c.y * k.aces_scale, c.z * k.aces_scale));
+    tm = aces_fit<EXACT>(mk3(c.x * k.aces_scale, c.y * k.aces_scale, c.z * k.aces_scale));
   } else {
     const f3 mean = mk3(lerpf(k.light_adapt, k.m0, c.x), lerpf(k.light_adapt, k.m1, c.y), lerpf(k.light_adapt, k.m2, c.z));
-    const f3 ad = mk3(pow_nz(mean.x * k.inv_exposure, k.key), pow_nz(mean.y * k.inv_exposure, k.key), pow_nz(mean.z * k.inv_exposure, k.key));  // key >= 0.3
-    if constexpr (MODE == TDK_TONEMAP_REINHARD) tm = mk3(tdk_div(c.x, ad.x + c.x), tdk_div(c.y, ad.y + c.y), tdk_div(c.z, ad.z + c.z));
-    else if constexpr (MODE == TDK_TONEMAP_LINEAR) tm = mk3(tdk_div(c.x, ad.x), tdk_div(c.y, ad.y), tdk_div(c.z, ad.z));
-    else tm = aces_fit(mk3(tdk_div(c.x, ad.x), tdk_div(c.y, ad.y), tdk_div(c.z, ad.z)));
+    // key in [0.3, 1]: a negative mean gives NaN as powf does, except for key == 1 (wave-uniform), where powf returns the base
+    auto adapt = [&](float m) { const float b = m * k.inv_exposure; return (EXACT && k.key_is_one) ? b : pow_nz(b, k.key); };
+    const f3 ad = mk3(adapt(mean.x), adapt(mean.y), adapt(mean.z));
+    // (the sum ad + c is formed unscaled: where it overflows, the reference's quotient is c / inf = 0)
+    if constexpr (MODE == TDK_TONEMAP_REINHARD) tm = mk3(dv(c.x, ad.x + c.x), dv(c.y, ad.y + c.y), dv(c.z, ad.z + c.z));
+    else if constexpr (MODE == TDK_TONEMAP_LINEAR) tm = mk3(dv(c.x, ad.x), dv(c.y, ad.y), dv(c.z, ad.z));
+    else tm = aces_fit<EXACT>(mk3(dv(c.x, ad.x), dv(c.y, ad.y), dv(c.z, ad.z)));
   }
   const f3 g = mk3(pw(fmaxf(tm.x, 0.0f), k.inv_gamma), pw(fmaxf(tm.y, 0.0f), k.inv_gamma), pw(fmaxf(tm.z, 0.0f), k.inv_gamma));
   // modify_rgb_vibrance_dt(g, amount) = clip(lab_to_rgb(scale(rgb_to_lab(g)))) (device_color_conversions.h:199-213).
@@ -304,10 +323,21 @@ template <int MODE, bool LEAN> __device__ __forceinline__ f3 tonemap_px(f3 c, co
   // error that is 2500x below one uint8 step.  The round trip is skipped (wave-uniform branch: `amount` is a
   // kernel argument); outputs differ from the reference only where its value sits within 1e-6 * 255 of a rounding
   // tie, the class of difference its own non-deterministic fast-math build already has (test_tonemaps_u8).
+  // One thing the round trip does decide: from g = 1.197e16 on (an infinite g included) the sRGB decode ((g + 0.055) / 1.055)^2.4
+  // overflows, inf - inf makes the Lab chroma NaN, and the reference's clip turns the WHOLE pixel to 0.
+  auto skip_round_trip = [&](f3 g) {
+    const f3 o = clip3(g);
+    const float m = fmaxf(fmaxf(g.x, g.y), g.z);
+    if constexpr (!EXACT) {
+      if constexpr (MODE == TDK_TONEMAP_LINEAR) *gmax = fmaxf(*gmax, m);
+      return o;
+    }
+    return m > TDK_LAB_OVERFLOW ? mk3(0.0f, 0.0f, 0.0f) : o;
+  };
   if constexpr (LEAN) {
-    return clip3(g);
+    return skip_round_trip(g);
   } else {
-    if (k.vibrance == 0.0f) return clip3(g);
+    if (k.vibrance == 0.0f) return skip_round_trip(g);
     f3 o = cB::vibrance(g, k.vibrance);
     if constexpr (MODE == TDK_TONEMAP_LINEAR) o = clip3(o);
     return o;
@@ -321,10 +351,13 @@ __device__ __forceinline__ TmConst make_consts(const float* metrics, float gamma
   k.vibrance = vibrance;
   k.light_adapt = light_adapt;
   k.aces_scale = 1.0f; k.key = 1.0f; k.inv_exposure = 1.0f; k.m0 = k.m1 = k.m2 = 0.0f;
+  k.key_is_one = false; k.mean_may_be_negative = false;
   if constexpr (MODE == TDK_TONEMAP_ACES) {
     k.aces_scale = tdk_pow(2.0f, intensity);
   } else {
     k.key = map_key_of(metrics[0]);
+    k.key_is_one = k.key == 1.0f;
+    k.mean_may_be_negative = fminf(fminf(metrics[2], metrics[3]), metrics[4]) < 0.0f || !(light_adapt >= 0.0f && light_adapt <= 1.0f);
     k.inv_exposure = 1.0f / tdk_exp(intensity);
     k.m0 = metrics[2]; k.m1 = metrics[3]; k.m2 = metrics[4];
   }
@@ -341,17 +374,57 @@ __global__ __launch_bounds__(256) void tonemap_vec4(const T* __restrict__ in, ui
   // issues at half rate on gfx950 (4.4 instead of 2.4 cycles, tests/hip_unit/valu_issue_bench.hip); they are used ~20 times
   // per pixel.  Through an empty asm they become VGPR values (one v_mov each, once per thread).
   asm volatile("" : "+v"(k.key), "+v"(k.inv_exposure), "+v"(k.m0), "+v"(k.m1), "+v"(k.m2), "+v"(k.inv_gamma), "+v"(k.light_adapt), "+v"(k.aces_scale));
+  auto store = [&](int64_t g, const uint32_t* b) {
+#pragma unroll
+    for (int w = 0; w < 3; w++) out[3 * g + w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
+  };
+  bool again = false;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256) {
     float v[12];
     rgb4_io<T>::load(in, g, v);
     uint32_t b[12];
+    if constexpr (LEAN) {
+      // the common path carries none of the EXACT form's extra instructions: it finds out, per group of four pixels, whether
+      // anything asks for them (a sample beyond 2^60 or infinite, a gamma-encoded value that overflows the skipped round trip,
+      // map_key == 1 together with a negative sample); the thread computes its groups again after this loop if any did
+      float amax = 0.0f, gmax = 0.0f, amin = 0.0f;
+      if constexpr (sizeof(T) == 4) {  // a finite binary16 sample is at most 65504, and an infinite one gives NaN -> 0 in both forms
 #pragma unroll
-    for (int p = 0; p < 4; p++) {
-      const f3 o = tonemap_px<MODE, LEAN>(mk3(v[3 * p], v[3 * p + 1], v[3 * p + 2]), k);  // clipped to [0, 1] by every mode
-      b[3 * p] = to_u8_clipped(o.x); b[3 * p + 1] = to_u8_clipped(o.y); b[3 * p + 2] = to_u8_clipped(o.z);
+        for (int i = 0; i < 12; i++) amax = fmaxf(amax, fabsf(v[i]));
+      }
+      if (k.key_is_one) {  // wave-uniform; a black frame: only a negative mean needs powf's x^1 = x
+#pragma unroll
+        for (int i = 0; i < 12; i++) amin = fminf(amin, v[i]);
+      }
+#pragma unroll
+      for (int p = 0; p < 4; p++) {
+        const f3 o = tonemap_px<MODE, true, false>(mk3(v[3 * p], v[3 * p + 1], v[3 * p + 2]), k, &gmax);
+        b[3 * p] = to_u8_clipped(o.x); b[3 * p + 1] = to_u8_clipped(o.y); b[3 * p + 2] = to_u8_clipped(o.z);
+      }
+      again = again || amax > TDK_TONEMAP_ORDINARY || gmax > TDK_LAB_OVERFLOW || (k.key_is_one && (amin < 0.0f || k.mean_may_be_negative));
+    } else {
+#pragma unroll
+      for (int p = 0; p < 4; p++) {
+        const f3 o = tonemap_px<MODE, false>(mk3(v[3 * p], v[3 * p + 1], v[3 * p + 2]), k);  // clipped to [0, 1] by every mode
+        b[3 * p] = to_u8_clipped(o.x); b[3 * p + 1] = to_u8_clipped(o.y); b[3 * p + 2] = to_u8_clipped(o.z);
+      }
     }
+    store(g, b);
+  }
+  if constexpr (LEAN) {
+    if (__builtin_expect(again, 0)) {  // rare: all of this thread's groups once more, in the EXACT form, over its own earlier stores
+      for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256) {
+        float v[12];
+        rgb4_io<T>::load(in, g, v);
+        uint32_t b[12];
 #pragma unroll
-    for (int w = 0; w < 3; w++) out[3 * g + w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
+        for (int p = 0; p < 4; p++) {
+          const f3 o = tonemap_px<MODE, true, true>(mk3(v[3 * p], v[3 * p + 1], v[3 * p + 2]), k);
+          b[3 * p] = to_u8_clipped(o.x); b[3 * p + 1] = to_u8_clipped(o.y); b[3 * p + 2] = to_u8_clipped(o.z);
+        }
+        store(g, b);
+      }
+    }
   }
 }
 
@@ -384,7 +457,8 @@ int run_tonemap(const void* rgb, uint8_t* out, int64_t npix, const float* metric
   int64_t done = 0;
   if (tdk_aligned(in, 16) && tdk_aligned(out, 4) && npix >= 4) {
     const int64_t ng = npix / 4;
-    if (vibrance == 0.0f && 1.0f / gamma != 0.0f)
+    const float ig = 1.0f / gamma;
+    if (vibrance == 0.0f && ig != 0.0f && (MODE == TDK_TONEMAP_LINEAR || ig <= 2.0f))
       TDK_LAUNCH("tdk_tonemap", (tonemap_vec4<T, MODE, true>), dim3(stream_grid(ng)), dim3(256), 0, s, in, reinterpret_cast<uint32_t*>(out), ng, metrics,
                          gamma, intensity, light_adapt, vibrance);
     else
