@@ -1,5 +1,5 @@
-"""CPU-only: a float64 restatement of the local Laplacian filter with explicit binary16 rounding at every store, against
-the C oracle (fp32 arithmetic, binary16 storage).
+"""CPU-only: a float64 restatement of the local Laplacian filter with explicit binary16 rounding at every store
+(tests/laplacian_spec.py), against the C oracle (fp32 arithmetic, binary16 storage).
 
 Written from the reference's formulas (csrc/local_contrast/laplacian.cu:50-66 sizes and boundary clamp, :111-141 expand,
 :177-207 reduce, :221-252 assemble, :266-290 curve, :482-592 sequencing) as whole-array numpy
@@ -10,106 +10,7 @@ i.e. by one binary16 ulp of the stored value, on a small share of the pixels -- 
 import numpy as np
 import pytest
 
-NG = 6
-K5 = np.array([1, 4, 6, 4, 1], np.float64) / 16
-
-
-def h16(a):
-    return np.asarray(a).astype(np.float16).astype(np.float64)  # write_imagef_half: every stored value is binary16
-
-
-def dl(x, level):
-    return (x + (1 << level) - 1) >> level
-
-
-def reduce_half(fine, cw, ch):
-    """5x5 binomial at 2c with c = the coarse position clamped to [1, size - 2] (laplacian.cu:177-207)."""
-    cx = np.clip(np.arange(cw), 1, cw - 2)
-    cy = np.clip(np.arange(ch), 1, ch - 2)
-    acc = np.zeros((ch, cw))
-    for j in range(-2, 3):
-        for i in range(-2, 3):
-            acc += fine[(2 * cy + j)[:, None], (2 * cx + i)[None, :]] * (K5[i + 2] * K5[j + 2])
-    return h16(acc)
-
-
-def expand(coarse, qx, qy):
-    """4 x (binomial taps of the zero-stuffed coarse level): 3 taps (1, 6, 1)/16 at an even coordinate, 2 taps (4, 4)/16 at
-    an odd one (laplacian.cu:111-141); qx / qy are coordinate arrays."""
-    def taps(q):
-        c = q // 2
-        odd = (q & 1) == 1
-        w = np.where(odd[None, :], np.array([0.0, 4.0, 4.0])[:, None], np.array([1.0, 6.0, 1.0])[:, None]) / 16  # offsets -1, 0, +1
-        return c, w
-    cx, wx = taps(qx)
-    cy, wy = taps(qy)
-    out = np.zeros((qy.size, qx.size))
-    for j in (-1, 0, 1):
-        for i in (-1, 0, 1):
-            wgt = wy[j + 1][:, None] * wx[i + 1][None, :]
-            # a zero-weight tap may point outside the level (offset -1 at coordinate 0 is never used: q >= 1)
-            out += wgt * coarse[np.clip(cy + j, 0, coarse.shape[0] - 1)[:, None], np.clip(cx + i, 0, coarse.shape[1] - 1)[None, :]]
-    return 4.0 * out
-
-
-def clamp_boundary(n):
-    """The fine coordinate an expand is evaluated at (laplacian.cu:53-65): [1, n - 2] for odd n, [1, n - 3] for even n."""
-    q = np.arange(n)
-    q = np.minimum(q, n - 2 if n & 1 else n - 3)
-    return np.maximum(q, 1)
-
-
-def curve(x, g, sigma, shadows, highlights, clarity):
-    c = x - g
-    pos = c > 0
-    ssigma = np.where(pos, sigma, -sigma)
-    shadhi = np.where(pos, shadows, highlights)
-    lin = g + ssigma + shadhi * (c - ssigma)
-    t = np.clip(c / (2.0 * ssigma), 0.0, 1.0)
-    bez = g + ssigma * 2.0 * (1.0 - t) * t + t * t * (ssigma + ssigma * shadhi)
-    val = np.where(np.abs(c) > 2 * sigma, lin, bez)
-    return val + clarity * c * np.exp(-c * c / (2.0 * sigma * sigma / 3.0))
-
-
-def laplacian_fp64(lum, sigma, shadows, highlights, clarity):
-    H, W = lum.shape
-    L = min(30, int(np.floor(np.log2(min(W, H)))))
-    pad = 1 << (L - 1)
-    bw, bh = W + 2 * pad, H + 2 * pad
-    size = [(dl(bh, l), dl(bw, l)) for l in range(L)]
-    ys, xs = np.clip(np.arange(bh) - pad, 0, H - 1), np.clip(np.arange(bw) - pad, 0, W - 1)
-    padded = [h16(lum.astype(np.float64)[ys[:, None], xs[None, :]])]
-    for l in range(1, L):
-        padded.append(reduce_half(padded[l - 1], size[l][1], size[l][0]))
-    proc = []
-    for k in range(NG):
-        g = np.float64(np.float32((k + 0.5) / NG))  # the reference forms g in fp32
-        p = [h16(curve(padded[0], g, sigma, shadows, highlights, clarity))]
-        for l in range(1, L):
-            p.append(reduce_half(p[l - 1], size[l][1], size[l][0]))
-        proc.append(p)
-    out = [None] * L
-    out[L - 1] = padded[L - 1]                      # the coarsest gaussian level lives in the output pyramid (:526)
-    for l in range(L - 2, -1, -1):
-        ph, pw = size[l]
-        qx, qy = clamp_boundary(pw), clamp_boundary(ph)
-        v = padded[l]
-        hi = np.ones(v.shape, int)
-        for h in range(1, NG - 1):                  # hi advances while (hi + .5) / NG <= v
-            hi += (hi == h) & (np.float64(np.float32((h + 0.5) / NG)) <= v)
-        lo = hi - 1
-        a = np.clip(v * NG - (lo + 0.5), 0.0, 1.0)
-        lap = [proc[k][l] - expand(proc[k][l + 1], qx, qy) for k in range(NG)]
-        lap = np.stack(lap)
-        yy, xx = np.mgrid[0:ph, 0:pw]
-        l0, l1 = lap[lo, yy, xx], lap[lo + 1, yy, xx]
-        out[l] = h16(expand(out[l + 1], qx, qy) + l0 * (1.0 - a) + l1 * a)
-    return out[0][pad:pad + H, pad:pad + W]
-
-
-def half_ulp_of(v):
-    e = np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** -14)))
-    return 2.0 ** (e - 10)
+from laplacian_spec import half_ulp_of, laplacian_fp64
 
 
 @pytest.mark.parametrize('size', [(40, 56), (33, 47), (64, 64)])

@@ -125,6 +125,11 @@ __device__ __forceinline__ float reduce25_half(const __half* __restrict__ fine, 
 // on every size / parameter set of the tests and of profiles/bounds_probe.py (level-1 kernel 128 -> 169 us, level-0 assemble
 // 93 -> 103 us at 12 MP: profiles/r04/experiments/laplacian_faithful_curve.txt) -- parity first.  The clarity term keeps the
 // hardware exp2 (the reference is a --use_fast_math build); per-launch constants are hoisted into CurveK.
+// The reference adds clarity * c * exp(..) for every clarity: at clarity 0 that is +-0 for a finite c and NaN for an infinite or
+// NaN one (0 * inf), so a non-finite sample is a NaN in all six gamma pyramids whatever the settings.  The clarity-free
+// instantiation keeps exactly that with `0.0f * c`: without it the select would hand a NaN sample the finite value g (fmaxf drops
+// the NaN of t) and an infinite one `lin` -- with a negative slope an infinity of the OTHER sign than the input pyramid's, and the
+// assemble then returns +-inf where the reference returns NaN.
 struct CurveK {
   float sigma, two_sigma, inv_two_sigma, shadows, highlights, clarity, neg_inv_e;  // neg_inv_e = -log2(e) / (2 sigma^2 / 3)
   bool plain_div;
@@ -149,6 +154,7 @@ template <bool HAS_CLARITY> __device__ __forceinline__ float curve(float x, floa
   if (__builtin_amdgcn_ballot_w64(!(fabsf(c) > k.two_sigma)) == 0) {
     float v = lin;
     if constexpr (HAS_CLARITY) v += k.clarity * c * __builtin_amdgcn_exp2f(c * c * k.neg_inv_e);
+    else v += 0.0f * c;
     return v;
   }
 #endif
@@ -168,6 +174,7 @@ template <bool HAS_CLARITY> __device__ __forceinline__ float curve(float x, floa
   const float bez = g + d * mt * t + t2 * (ssigma + ssigma * shadhi);  // ssigma * 2.0f == d
   float val = (fabsf(c) > k.two_sigma) ? lin : bez;
   if constexpr (HAS_CLARITY) val += k.clarity * c * __builtin_amdgcn_exp2f(c * c * k.neg_inv_e);  // hardware exp2 (fast-math build)
+  else val += 0.0f * c;
   return val;
 }
 __device__ __forceinline__ float gamma_centre(int k) { return ((float)k + 0.5f) / (float)NG; }
@@ -359,18 +366,24 @@ __host__ __device__ __forceinline__ int clamp_boundary(int q, int n) {
 }
 
 // laplacian.cu:111-141 on any coarse-level accessor: an even coordinate uses taps -1, 0, 1 with weights 1 6 1, an
-// odd one taps 0, 1 with weights 4 4.  Same taps, weights and summation order as the reference's loops; the tap
-// an odd coordinate skips gets weight 0 (adds an exact +0) instead of a branch.
+// odd one taps 0, 1 with weights 4 4.  Same taps, weights and summation order as the reference's loops.  The tap an
+// odd coordinate skips is still fetched (no branch) but a select keeps it out of the sum: the reference never reads that
+// cell, so a NaN or an infinity in it must not reach the result -- a weight of 0 would turn it into a NaN.  The select adds
+// an exact +0, which leaves every finite sum's bits as they are.
 template <typename F> __device__ __forceinline__ float expand4(F coarse, int x, int y) {
   const int cx = x / 2, cy = y / 2;
   const bool x_odd = x & 1, y_odd = y & 1;
-  const float wx[3] = {x_odd ? 0.0f : 1.0f / 16.0f, x_odd ? 4.0f / 16.0f : 6.0f / 16.0f, x_odd ? 4.0f / 16.0f : 1.0f / 16.0f};
-  const float wy[3] = {y_odd ? 0.0f : 1.0f / 16.0f, y_odd ? 4.0f / 16.0f : 6.0f / 16.0f, y_odd ? 4.0f / 16.0f : 1.0f / 16.0f};
+  const float wx[3] = {1.0f / 16.0f, x_odd ? 4.0f / 16.0f : 6.0f / 16.0f, x_odd ? 4.0f / 16.0f : 1.0f / 16.0f};
+  const float wy[3] = {1.0f / 16.0f, y_odd ? 4.0f / 16.0f : 6.0f / 16.0f, y_odd ? 4.0f / 16.0f : 1.0f / 16.0f};
   float c = 0.0f;
 #pragma unroll
   for (int i = -1; i <= 1; i++)
 #pragma unroll
-    for (int j = -1; j <= 1; j++) c += coarse(cx + i, cy + j) * wx[i + 1] * wy[j + 1];
+    for (int j = -1; j <= 1; j++) {
+      const float term = coarse(cx + i, cy + j) * wx[i + 1] * wy[j + 1];
+      const bool skipped = (i < 0 && x_odd) || (j < 0 && y_odd);
+      c += skipped ? 0.0f : term;
+    }
   return 4.0f * c;
 }
 
@@ -427,7 +440,7 @@ __global__ __launch_bounds__(256) void assemble_tiled_kernel(Layout L, int l, co
     if (y >= fh) break;
     if (LEVEL0 && (y < L.pad || y >= L.pad + L.h)) continue;
     const int qy = clamp_boundary(y, fh);
-    // index clamps only matter for taps of weight 0
+    // index clamps only matter for taps expand4 keeps out of its sum
     auto tile = [&](int k, int i, int j) { return tiles[k * (ACH * ACS) + max(j - ty0, 0) * ACS + max(i - tx0, 0)]; };
     float v;
     if constexpr (LEVEL0) v = round_half(ld<T>(image, (size_t)(y - L.pad) * L.w + (x - L.pad)));
@@ -463,7 +476,7 @@ __global__ __launch_bounds__(1024) void deep_assemble_kernel(Layout L, Rects nee
     for (int i = threadIdx.x; i < rw * rh; i += 1024) {
       const int yy = i / rw, x = rc.x0 + (i - yy * rw), y = rc.y0 + yy;
       const float v = hld(L.at(0, l), x, y, fw);
-      auto cell = [&](int k, int ci, int cj) { return __half2float(coarse[k * cells + max(cj, 0) * cw + max(ci, 0)]); };  // -1 only under weight 0
+      auto cell = [&](int k, int ci, int cj) { return __half2float(coarse[k * cells + max(cj, 0) * cw + max(ci, 0)]); };  // -1 only for a tap expand4 keeps out of its sum
       const float val = assemble_px(
           v, clamp_boundary(x, fw), clamp_boundary(y, fh), [&](int ci, int cj) { return cell(0, ci, cj); },
           [&](int k, int ci, int cj) { return cell(1 + k, ci, cj); }, [&](int k) { return hld(L.at(2 + k, l), x, y, fw); });
