@@ -1,7 +1,7 @@
 """Run one op of the hot path a few times on synthetic 12 MP data -- the target of the
 rocprofv3 passes whose summaries are committed in this directory.
 
-  python profiles/run_op.py {rcd,ppg,postprocess,wiener,bilateral,laplacian,tonemap,luminance,jpeg,isp,isp_jpeg} [--iters N] [--storage f16|f32]
+  python profiles/run_op.py {rcd,ppg,postprocess,wiener,bilateral,laplacian,tonemap,luminance,jpeg,isp,isp_jpeg,temporal} [--iters N] [--storage f16|f32]
 """
 import argparse
 import sys
@@ -47,6 +47,12 @@ def main():
     acc = td.tonemap.MetricsAccumulator(dev, stride=8)
     jpeg = td.Jpeg()
     u8 = td.reinhard_tonemap(rgb, metrics, params)
+    temporal = None
+    if a.op == 'temporal':  # a static scene with read noise of sigma 0.004, radius 2; five frames of history before the counted ones
+        ring = [(bayer.float().view(h, w) + 0.004 * torch.randn((h, w), device=dev)).to(dt) for _ in range(4)]
+        temporal = td.TemporalDenoise(dev, (w, h), td.BayerPattern.RGGB, td.NoiseModel.from_values(0.0, 1.6e-5, dev), state_dtype=dt)
+        for i in range(5):
+            temporal.process(ring[i & 3])
     torch.cuda.synchronize()
     for _ in range(a.iters):
         if a.op == 'rcd':
@@ -79,6 +85,8 @@ def main():
             jpeg.encode(td.reinhard_tonemap(x, acc.finish(), params))
         elif a.op == 'jpeg':
             jpeg.encode(u8)
+        elif a.op == 'temporal':
+            temporal.process(ring[_ & 3])
         elif a.op == 'isp_rgb':  # the same chain with the intermediate RGB image materialised (bench.py --chain rgb)
             with td.torch_darktable_extension.concurrent_frames():
                 x = rcd.process(bayer)

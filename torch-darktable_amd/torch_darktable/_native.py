@@ -179,6 +179,16 @@ NOISE_SIGNATURES = {
   'tdk_noise_unstabilize': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_uint32, c_void_p, c_void_p, c_float, c_int, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_temporal.h, the temporal denoiser (src, out, state, model, gains: device pointers)
+TEMPORAL_SIGNATURES = {
+  'tdk_temporal_abi_version': (c_int, []),
+  'tdk_temporal_state_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_temporal_lds_bytes': (c_size_t, [c_int]),
+  'tdk_temporal_reset': (c_int, [c_void_p, c_void_p]),
+  'tdk_temporal_denoise': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p, c_int, c_float, c_float,
+                                   c_float, c_float, c_float, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_lut.h, the colour transform (matrix, lut_lo, lut_scale: host pointers; shaper, lut: device pointers)
 LUT_SIGNATURES = {
   'tdk_lut_abi_version': (c_int, []),
@@ -199,6 +209,7 @@ HEADERS = (
   ('tdk_hip_sharpen.h', SHARPEN_SIGNATURES, 'tdk_sharpen_abi_version', 1, 'sharpen ABI'),
   ('tdk_hip_wavelet.h', WAVELET_SIGNATURES, 'tdk_wavelet_abi_version', 1, 'wavelet ABI'),
   ('tdk_hip_highlights.h', HIGHLIGHTS_SIGNATURES, 'tdk_highlights_abi_version', 1, 'highlights ABI'),
+  ('tdk_hip_temporal.h', TEMPORAL_SIGNATURES, 'tdk_temporal_abi_version', 1, 'temporal ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
@@ -228,6 +239,9 @@ TDK_NOISE_MAX_BINS, TDK_NOISE_MAX_FRAMES, TDK_NOISE_LEVELS = 32, 16, 128
 TDK_NOISE_GRID, TDK_NOISE_STRIP_BYTES = 512, 512
 TDK_NOISE_MEDIAN_FACTOR = 0.9796
 TDK_NOISE_ALGEBRAIC, TDK_NOISE_UNBIASED = 0, 1  # inverse of tdk_noise_unstabilize
+# include/tdk_hip_temporal.h: the output tile of a workgroup of tdk_temporal_denoise, the head of its state, the largest n_max
+TDK_TEMPORAL_TILE_W, TDK_TEMPORAL_TILE_H = 64, 32
+TDK_TEMPORAL_HEAD_BYTES, TDK_TEMPORAL_MAX_FRAMES = 16, 64
 
 
 def load() -> C.CDLL:

@@ -1,4 +1,4 @@
-"""packed raw bytes -> uint8 RGB: decode -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
+"""packed raw bytes -> uint8 RGB: decode -> [temporal denoise of the raw mosaic] -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
 [wavelet chroma denoise, with `noise_model` inside the variance-stabilising transform] -> [colour transform] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
@@ -26,6 +26,7 @@ from ..noiseprofile import NoiseModel
 from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
+from ..temporal import TemporalDenoise
 from ..wavelet import Wavelet
 from ..white_balance import apply_white_balance
 from .camera_settings import CameraSettings
@@ -48,7 +49,7 @@ class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
-                 storage_dtype: torch.dtype = torch.float32, exposure: FrameStats | None = None, noise_model: NoiseModel | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
+                 storage_dtype: torch.dtype = torch.float32, temporal: TemporalDenoise | None = None, exposure: FrameStats | None = None, noise_model: NoiseModel | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
                  sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
         assert device.index is not None, f'Device not fully specified: {device}'
@@ -68,6 +69,14 @@ class ImageProcessor:
             raise ValueError(f'raw_correction is for {raw_correction.image_size} {raw_correction.bayer_pattern.name}, '
                              f'the processor for {tuple(image_size)} {bayer_pattern.name}')
         self.raw_correction = raw_correction
+        # recursive temporal denoiser on the linear mosaic without gains (where its noise model was measured), one sequence per
+        # image name, in front of the white balance; load_image then takes the unfused path; None: the reference's chain
+        if temporal is not None:
+            if not isinstance(temporal, TemporalDenoise):
+                raise TypeError(f'temporal must be a TemporalDenoise or None, got {type(temporal).__name__} (pass the arguments behind storage_dtype by keyword)')
+            if temporal.image_size != tuple(image_size) or temporal.bayer_pattern != bayer_pattern:
+                raise ValueError(f'temporal is for {temporal.image_size} {temporal.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+        self.temporal = temporal
         # output sharpening of the tone-mapped uint8 frame, after the scaler and before the orientation; None: the reference's chain
         if sharpen is not None and not isinstance(sharpen, Sharpen):
             raise TypeError(f'sharpen must be a Sharpen or None, got {type(sharpen).__name__} (raw_correction is the argument after it: pass both by keyword)')
@@ -209,7 +218,24 @@ class ImageProcessor:
             raise self._mismatch(f'Decoded image size mismatch: expected {w * h} pixels ({w}x{h}), got {decoded.numel()} pixels.')
         return decoded.view(h, w)
 
-    def load_image(self, bytes: torch.Tensor) -> torch.Tensor:
+    def load_image(self, bytes: torch.Tensor, image_name: str | None = None) -> torch.Tensor:
+        if self.temporal is not None:
+            # the filter sees the linear mosaic as the noise model does: sensor correction without gains (or the plain decode) ->
+            # temporal (the sequence of this image name) -> highlights or white balance -> demosaic
+            if self.raw_correction is not None:
+                if bytes.numel() != self.expected_bytes:
+                    raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
+                                         f'with {self.padding} padding, got {bytes.numel()} bytes. ')
+                payload = bytes[: bytes.numel() - self.padding] if self.padding > 0 else bytes
+                mosaic = self.raw_correction.process_packed(payload, self.packed_format, white_balance=None)
+            else:
+                mosaic = self.load_bytes(bytes)
+            mosaic = self.temporal.process(mosaic, key=image_name)
+            if self.highlights is not None:
+                mosaic = self.highlights.process(mosaic, self.white_balance)
+            elif self.white_balance is not None:
+                mosaic = apply_white_balance(mosaic, self.white_balance, self.bayer_pattern)
+            return self._demosaic(mosaic).to(self.storage_dtype)
         if self.highlights is not None:
             # the gains are applied by the highlight stage, on the linear mosaic: sensor correction without gains (or the plain
             # decode) -> highlights -> demosaic; the fused decode + white balance + RCD kernel has no place for it
@@ -328,7 +354,10 @@ class ImageProcessor:
             raise self._resize_error
         names = list(image_set_bytes.keys())
         ema = self.settings.moving_average
-        rgb = [self.load_image(b) for b in image_set_bytes.values()]
+        if self.temporal is not None:   # the image name is the key of the frame's history; without the stage the call is what it was
+            rgb = [self.load_image(b, name) for name, b in image_set_bytes.items()]
+        else:
+            rgb = [self.load_image(b) for b in image_set_bytes.values()]
         if self.chroma_denoise is not None and self.noise_model is not None:
             m, wb = self.noise_model, self.white_balance
             rgb = [m.unstabilize(self.chroma_denoise.process(m.stabilize(img, gains=wb)), gains=wb, out_dtype=img.dtype) for img in rgb]
