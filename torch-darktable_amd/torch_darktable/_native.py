@@ -207,6 +207,14 @@ MOTION_SIGNATURES = {
                                           c_float, c_float, c_float, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_hdr.h, the exposure-bracket merge (frames: a host array of device pointers; the others device pointers)
+HDR_SIGNATURES = {
+  'tdk_hdr_abi_version': (c_int, []),
+  'tdk_hdr_lds_bytes': (c_size_t, [c_int]),
+  'tdk_hdr_merge': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_float,
+                            c_float, c_float, c_void_p]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -221,6 +229,7 @@ HEADERS = (
   ('tdk_hip_highlights.h', HIGHLIGHTS_SIGNATURES, 'tdk_highlights_abi_version', 1, 'highlights ABI'),
   ('tdk_hip_temporal.h', TEMPORAL_SIGNATURES, 'tdk_temporal_abi_version', 1, 'temporal ABI'),
   ('tdk_hip_motion.h', MOTION_SIGNATURES, 'tdk_motion_abi_version', 1, 'motion ABI'),
+  ('tdk_hip_hdr.h', HDR_SIGNATURES, 'tdk_hdr_abi_version', 1, 'hdr ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
@@ -256,6 +265,9 @@ TDK_TEMPORAL_HEAD_BYTES, TDK_TEMPORAL_MAX_FRAMES = 16, 64
 # include/tdk_hip_motion.h: the tile of one displacement, the limits of tdk_motion_pyramid and tdk_motion_match
 TDK_MOTION_TILE_W, TDK_MOTION_TILE_H = 64, 32
 TDK_MOTION_MAX_LEVELS, TDK_MOTION_MAX_SEARCH, TDK_MOTION_MAX_DISPLACEMENT, TDK_MOTION_MAX_ZERO_BIAS = 4, 4, 78, 65535
+# include/tdk_hip_hdr.h: the output tile of a workgroup of tdk_hdr_merge, the largest bracket
+TDK_HDR_TILE_W, TDK_HDR_TILE_H = 32, 32
+TDK_HDR_MAX_FRAMES = 8
 
 
 def load() -> C.CDLL:

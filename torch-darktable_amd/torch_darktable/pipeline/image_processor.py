@@ -1,4 +1,4 @@
-"""packed raw bytes -> uint8 RGB: decode -> [temporal denoise of the raw mosaic] -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
+"""packed raw bytes -> uint8 RGB: decode -> [temporal denoise of the raw mosaic | merge of an exposure bracket (process_bracket)] -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
 [wavelet chroma denoise, with `noise_model` inside the variance-stabilising transform] -> [colour transform] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
@@ -20,6 +20,7 @@ from ..bayer import BayerPattern, PackedFormat
 from ..colorlut import ColorLUT
 from ..denoise import Wiener
 from ..framestats import FrameStats
+from ..hdrmerge import HdrMerge
 from ..highlights import Highlights
 from ..local_contrast import Bilateral
 from ..noiseprofile import NoiseModel
@@ -48,7 +49,7 @@ class ImageSizeMismatchError(Exception):
 class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
-                 transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0,
+                 transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0, hdr: HdrMerge | None = None,
                  storage_dtype: torch.dtype = torch.float32, temporal: TemporalDenoise | None = None, exposure: FrameStats | None = None, noise_model: NoiseModel | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
                  sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
@@ -77,6 +78,13 @@ class ImageProcessor:
             if temporal.image_size != tuple(image_size) or temporal.bayer_pattern != bayer_pattern:
                 raise ValueError(f'temporal is for {temporal.image_size} {temporal.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
         self.temporal = temporal
+        # merge of an exposure bracket on the linear mosaics without gains, for process_bracket; None: the processor takes no brackets
+        if hdr is not None:
+            if not isinstance(hdr, HdrMerge):
+                raise TypeError(f'hdr must be an HdrMerge or None, got {type(hdr).__name__} (pass the arguments behind padding by keyword)')
+            if hdr.image_size != tuple(image_size) or hdr.bayer_pattern != bayer_pattern:
+                raise ValueError(f'hdr is for {hdr.image_size} {hdr.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+        self.hdr = hdr
         # output sharpening of the tone-mapped uint8 frame, after the scaler and before the orientation; None: the reference's chain
         if sharpen is not None and not isinstance(sharpen, Sharpen):
             raise TypeError(f'sharpen must be a Sharpen or None, got {type(sharpen).__name__} (raw_correction is the argument after it: pass both by keyword)')
@@ -267,6 +275,31 @@ class ImageProcessor:
             return self.postprocess_workspace.process(rgb) if self.settings.postprocess else rgb
         return self.debayer(self.load_bytes(bytes)).to(self.storage_dtype)
 
+    def load_bracket(self, payloads, exposures, ref: int | None = None) -> torch.Tensor:
+        """The packed frames of one exposure bracket -> the demosaiced merge: every payload becomes the linear mosaic without gains
+        (sensor correction, or the plain decode), `hdr` merges them, and the merged mosaic goes on as load_image's does: highlights or
+        white balance -> demosaic."""
+        if self.hdr is None:
+            raise ValueError('process_bracket needs hdr: build the processor with hdr=HdrMerge(...)')
+        if self.temporal is not None:
+            raise ValueError('process_bracket and temporal do not combine: the frames of a bracket are no sequence of one exposure')
+        mosaics = []
+        for bytes in payloads:
+            if self.raw_correction is not None:
+                if bytes.numel() != self.expected_bytes:
+                    raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
+                                         f'with {self.padding} padding, got {bytes.numel()} bytes. ')
+                payload = bytes[: bytes.numel() - self.padding] if self.padding > 0 else bytes
+                mosaics.append(self.raw_correction.process_packed(payload, self.packed_format, white_balance=None))
+            else:
+                mosaics.append(self.load_bytes(bytes))
+        mosaic = self.hdr.process(mosaics, exposures, ref=ref)
+        if self.highlights is not None:
+            mosaic = self.highlights.process(mosaic, self.white_balance)
+        elif self.white_balance is not None:
+            mosaic = apply_white_balance(mosaic, self.white_balance, self.bayer_pattern)
+        return self._demosaic(mosaic).to(self.storage_dtype)
+
     def debayer(self, bayer_image: torch.Tensor) -> torch.Tensor:
         assert bayer_image.ndim == 2, f'Bayer image must have 2 dimensions, got {bayer_image.shape}'
         if self.white_balance is not None:
@@ -335,6 +368,12 @@ class ImageProcessor:
     def process(self, bytes: torch.Tensor, image_name: str) -> torch.Tensor:
         return self.process_image_set({image_name: bytes})[image_name]
 
+    def process_bracket(self, payloads, exposures, image_name: str, ref: int | None = None) -> torch.Tensor:
+        """`process` of one exposure bracket: the packed frames are merged on the raw mosaic by `hdr` (exposures, ref: HdrMerge.process)
+        and the merge continues as `process` does from the mosaic on, bounds and metrics included."""
+        rgb = self.load_bracket(payloads, exposures, ref)
+        return self._process_frames([image_name], [rgb], resized=False)[image_name]
+
     def process_image_set(self, image_set_bytes: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         """One synchronised set of cameras: shared bounds / metrics (moving-averaged across calls)."""
         return self._process_image_set(image_set_bytes, resized=False)
@@ -353,11 +392,15 @@ class ImageProcessor:
         if resized and self._resize_error is not None:
             raise self._resize_error
         names = list(image_set_bytes.keys())
-        ema = self.settings.moving_average
         if self.temporal is not None:   # the image name is the key of the frame's history; without the stage the call is what it was
             rgb = [self.load_image(b, name) for name, b in image_set_bytes.items()]
         else:
             rgb = [self.load_image(b) for b in image_set_bytes.values()]
+        return self._process_frames(names, rgb, resized)
+
+    def _process_frames(self, names: list[str], rgb: list[torch.Tensor], resized: bool) -> dict[str, torch.Tensor]:
+        """From the demosaiced frames of a set on."""
+        ema = self.settings.moving_average
         if self.chroma_denoise is not None and self.noise_model is not None:
             m, wb = self.noise_model, self.white_balance
             rgb = [m.unstabilize(self.chroma_denoise.process(m.stabilize(img, gains=wb)), gains=wb, out_dtype=img.dtype) for img in rgb]
