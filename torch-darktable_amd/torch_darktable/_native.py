@@ -215,6 +215,16 @@ HDR_SIGNATURES = {
                             c_float, c_float, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_ca.h, the chromatic aberration (frames: a host array of device pointers; the others device pointers)
+CA_SIGNATURES = {
+  'tdk_ca_abi_version': (c_int, []),
+  'tdk_ca_lds_bytes': (c_size_t, [c_int, c_int]),
+  'tdk_ca_correct': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_uint32, c_void_p, c_float, c_float, c_float, c_int, c_void_p]),
+  'tdk_ca_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_ca_estimate': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_void_p, c_int, c_float, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                              c_void_p]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -230,6 +240,7 @@ HEADERS = (
   ('tdk_hip_temporal.h', TEMPORAL_SIGNATURES, 'tdk_temporal_abi_version', 1, 'temporal ABI'),
   ('tdk_hip_motion.h', MOTION_SIGNATURES, 'tdk_motion_abi_version', 1, 'motion ABI'),
   ('tdk_hip_hdr.h', HDR_SIGNATURES, 'tdk_hdr_abi_version', 1, 'hdr ABI'),
+  ('tdk_hip_ca.h', CA_SIGNATURES, 'tdk_ca_abi_version', 1, 'chromatic aberration ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
@@ -268,6 +279,13 @@ TDK_MOTION_MAX_LEVELS, TDK_MOTION_MAX_SEARCH, TDK_MOTION_MAX_DISPLACEMENT, TDK_M
 # include/tdk_hip_hdr.h: the output tile of a workgroup of tdk_hdr_merge, the largest bracket
 TDK_HDR_TILE_W, TDK_HDR_TILE_H = 32, 32
 TDK_HDR_MAX_FRAMES = 8
+# include/tdk_hip_ca.h: the largest displacement, the output tile of a workgroup of tdk_ca_correct, interp, fit, the limits of tdk_ca_estimate
+TDK_CA_MAX_SHIFT = 8
+TDK_CA_TILE_W, TDK_CA_TILE_H = 64, 32
+TDK_CA_BILINEAR, TDK_CA_BICUBIC = 0, 1
+TDK_CA_LINEAR, TDK_CA_POLY3 = 0, 1
+TDK_CA_MAX_FRAMES, TDK_CA_SUMS, TDK_CA_MIN_SITES = 16, 17, 16
+TDK_CA_QSCALE, TDK_CA_QMAX = 65535.0, 65535
 
 
 def load() -> C.CDLL:

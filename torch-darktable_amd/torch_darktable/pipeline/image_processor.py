@@ -1,4 +1,4 @@
-"""packed raw bytes -> uint8 RGB: decode -> [temporal denoise of the raw mosaic | merge of an exposure bracket (process_bracket)] -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
+"""packed raw bytes -> uint8 RGB: decode -> [temporal denoise of the raw mosaic | merge of an exposure bracket (process_bracket)] -> [chromatic aberration] -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
 [wavelet chroma denoise, with `noise_model` inside the variance-stabilising transform] -> [colour transform] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
@@ -17,6 +17,7 @@ import torch
 from .. import debayer as _debayer
 from .. import tonemap as _tonemap
 from ..bayer import BayerPattern, PackedFormat
+from ..chromatic import ChromaticAberration
 from ..colorlut import ColorLUT
 from ..denoise import Wiener
 from ..framestats import FrameStats
@@ -49,7 +50,7 @@ class ImageSizeMismatchError(Exception):
 class ImageProcessor:
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
-                 transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, padding: int = 0, hdr: HdrMerge | None = None,
+                 transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, chromatic: ChromaticAberration | None = None, padding: int = 0, hdr: HdrMerge | None = None,
                  storage_dtype: torch.dtype = torch.float32, temporal: TemporalDenoise | None = None, exposure: FrameStats | None = None, noise_model: NoiseModel | None = None, highlights: Highlights | None = None, color: ColorLUT | None = None, look: ColorLUT | None = None,
                  sharpen: Sharpen | None = None, chroma_denoise: Wavelet | None = None,
                  raw_correction: RawPrepare | None = None):
@@ -85,6 +86,15 @@ class ImageProcessor:
             if hdr.image_size != tuple(image_size) or hdr.bayer_pattern != bayer_pattern:
                 raise ValueError(f'hdr is for {hdr.image_size} {hdr.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
         self.hdr = hdr
+        # lateral chromatic aberration: the red and the blue plane of the linear mosaic are resampled onto the green one, behind the
+        # decode (or raw_correction, temporal, hdr) and in front of highlights or the white balance; load_image then takes the unfused
+        # path; None: the reference's chain.  (Every slot behind padding is pinned by the test of an earlier stage.)
+        if chromatic is not None:
+            if not isinstance(chromatic, ChromaticAberration):
+                raise TypeError(f'chromatic must be a ChromaticAberration or None, got {type(chromatic).__name__} (pass it and padding by keyword)')
+            if chromatic.image_size != tuple(image_size) or chromatic.bayer_pattern != bayer_pattern:
+                raise ValueError(f'chromatic is for {chromatic.image_size} {chromatic.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+        self.chromatic = chromatic
         # output sharpening of the tone-mapped uint8 frame, after the scaler and before the orientation; None: the reference's chain
         if sharpen is not None and not isinstance(sharpen, Sharpen):
             raise TypeError(f'sharpen must be a Sharpen or None, got {type(sharpen).__name__} (raw_correction is the argument after it: pass both by keyword)')
@@ -239,14 +249,17 @@ class ImageProcessor:
             else:
                 mosaic = self.load_bytes(bytes)
             mosaic = self.temporal.process(mosaic, key=image_name)
+            if self.chromatic is not None:
+                mosaic = self.chromatic.correct(mosaic)
             if self.highlights is not None:
                 mosaic = self.highlights.process(mosaic, self.white_balance)
             elif self.white_balance is not None:
                 mosaic = apply_white_balance(mosaic, self.white_balance, self.bayer_pattern)
             return self._demosaic(mosaic).to(self.storage_dtype)
-        if self.highlights is not None:
+        if self.highlights is not None or self.chromatic is not None:
             # the gains are applied by the highlight stage, on the linear mosaic: sensor correction without gains (or the plain
-            # decode) -> highlights -> demosaic; the fused decode + white balance + RCD kernel has no place for it
+            # decode) -> [chromatic aberration] -> highlights or white balance -> demosaic; the fused decode + white balance + RCD
+            # kernel has no place for either
             if self.raw_correction is not None:
                 if bytes.numel() != self.expected_bytes:
                     raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
@@ -255,7 +268,13 @@ class ImageProcessor:
                 mosaic = self.raw_correction.process_packed(payload, self.packed_format, white_balance=None)
             else:
                 mosaic = self.load_bytes(bytes)
-            return self._demosaic(self.highlights.process(mosaic, self.white_balance)).to(self.storage_dtype)
+            if self.chromatic is not None:
+                mosaic = self.chromatic.correct(mosaic)
+            if self.highlights is not None:
+                mosaic = self.highlights.process(mosaic, self.white_balance)
+            elif self.white_balance is not None:
+                mosaic = apply_white_balance(mosaic, self.white_balance, self.bayer_pattern)
+            return self._demosaic(mosaic).to(self.storage_dtype)
         if self.raw_correction is not None:
             if bytes.numel() != self.expected_bytes:
                 raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
@@ -294,6 +313,8 @@ class ImageProcessor:
             else:
                 mosaics.append(self.load_bytes(bytes))
         mosaic = self.hdr.process(mosaics, exposures, ref=ref)
+        if self.chromatic is not None:
+            mosaic = self.chromatic.correct(mosaic)
         if self.highlights is not None:
             mosaic = self.highlights.process(mosaic, self.white_balance)
         elif self.white_balance is not None:
