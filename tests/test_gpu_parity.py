@@ -4,7 +4,9 @@ C ABI -> kernels), against the CPU oracle on the same seeded inputs.
 Tolerance ladder (the reference itself is a fast-math CUDA build whose
 atomics are order-nondeterministic and ships no golden vectors, so parity is "unpinned" by the
 reference and anchored on the oracle's literal restatement):
-  T0 bit-exact  : codec, bilinear, PPG, RCD, colour smoothing, local green eq, white balance, bilateral
+  T0 bit-exact  : codec, bilinear, PPG, RCD, colour smoothing, local green eq, white balance, bilateral.  For bilinear, PPG, the
+                  PostProcess stages and the white balance the promise covers ALL float32 and binary16 inputs -- negative, tied,
+                  subnormal, overflowing, inf, NaN -- with NaN at exactly the oracle's positions (test_gpu_demosaic_domain.py)
   T1 sum order  : global green eq -- the ratio of two fp32 sums taken in different association orders; bound derived
                   in test_postprocess_global_green_eq from the block counts (a few 1e-6 relative)
   T2 1e-5..1e-4 : anything with powf/expf/logf/cbrtf, bilateral / Wiener (sum order)

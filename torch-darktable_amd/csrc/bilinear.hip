@@ -9,8 +9,17 @@
 // MI355X design: 256-thread workgroup, 128 x 16 pixel tile staged once through LDS with a 2-px
 // clamped halo (coalesced row reads); every thread produces a 4 x 2 pixel block so each output
 // row segment leaves as three 16-B stores (48 contiguous bytes per thread, 1.5 KiB per wave
-// row).  The kernel is instantiated per pattern, so all 13 x 3 weights are immediates and the
-// zero taps vanish.  Bit-exact against the oracle: same term order, no FMA, /16 == *0.0625.
+// row).  The kernel is instantiated per pattern, so all 13 x 3 weights are immediates.
+//
+// The oracle's bits over the whole float32 / binary16 domain, NaN positions included: same term order, no FMA, /16 == *0.0625.
+// The reference adds w * v for all 13 taps, so a zero-weight tap on an inf or NaN sample is 0 * inf = NaN in that channel.  While
+// staging, the workgroup notes whether its tile + halo holds a non-finite sample (one class test per staged sample, one vote per
+// wave through LDS around the barrier that was there already):
+//   all finite (every ordinary frame): the zero taps are dropped -- adding +-0 to the sum changes no value (FULL = false);
+//   otherwise: the full 13-tap product, as the oracle writes it (FULL = true).
+// Cost of the test at 4096 x 3072 on the finite scene, median of 5 x 40 launches, parent -> this kernel:
+//   f32 53.2 -> 54.4 us (+2.3 %), f16 30.5 -> 31.0 us (+1.6 %); the parent's own spread is 0.1 us
+//   (profiles/demosaic_domain_bench.py, profiles/r21/demosaic_domain_bench.txt).
 #include "tdk_common.h"
 
 namespace {
@@ -46,37 +55,29 @@ constexpr int LW = TW + 2 * HALO;      // 132
 constexpr int LH = TH + 2 * HALO;      // 20
 constexpr int LSTRIDE = LW + 1;        // odd stride keeps the two wave halves on different banks
 
-template <int CLS, int CH> __device__ __forceinline__ float apply(const float v[NTAP]) {
+// FULL: every tap enters as a product, zero weights too (0 * inf = 0 * NaN = NaN, as in the reference); otherwise -- all 13 samples
+// finite -- the zero taps are dropped, which changes no value
+template <int CLS, int CH, bool FULL> __device__ __forceinline__ float apply(const float v[NTAP]) {
   constexpr Taps f = filter_of<CLS, CH>();
   float acc = 0.0f;
 #pragma unroll
   for (int k = 0; k < NTAP; k++)
-    if (f.w[k] != 0) acc += (float)f.w[k] * v[k];
+    if (FULL || f.w[k] != 0) acc += (float)f.w[k] * v[k];
   return acc * 0.0625f;
 }
 
-template <int CLS> __device__ __forceinline__ void pixel(const float* t, int lx, int ly, float out[3]) {
+template <int CLS, bool FULL> __device__ __forceinline__ void pixel(const float* t, int lx, int ly, float out[3]) {
   float v[NTAP];
 #pragma unroll
   for (int k = 0; k < NTAP; k++) v[k] = t[(ly + TAP_DY[k]) * LSTRIDE + lx + TAP_DX[k]];
-  out[0] = apply<CLS, 0>(v);
-  out[1] = apply<CLS, 1>(v);
-  out[2] = apply<CLS, 2>(v);
+  out[0] = apply<CLS, 0, FULL>(v);
+  out[1] = apply<CLS, 1, FULL>(v);
+  out[2] = apply<CLS, 2, FULL>(v);
 }
 
-template <typename T, int PAT>
-__global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ in, T* __restrict__ out, int width, int height,
-                                                       int vec_ok) {
-  __shared__ float tile[LH * LSTRIDE];
-  const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
-  for (int i = threadIdx.x; i < LW * LH; i += 256) {
-    const int r = i / LW, c = i - r * LW;
-    const int gx = min(max(tx0 - HALO + c, 0), width - 1);
-    const int gy = min(max(ty0 - HALO + r, 0), height - 1);
-    tile[r * LSTRIDE + c] = ld(in, (size_t)gy * width + gx);
-  }
-  __syncthreads();
-
+// the 4 x 2 pixel block of one thread, from the staged tile
+template <typename T, int PAT, bool FULL>
+__device__ __forceinline__ void bilinear_block(const float* __restrict__ tile, T* __restrict__ out, int width, int height, int vec_ok, int tx0, int ty0) {
   const int lx = (threadIdx.x & 31) * 4, ly = (threadIdx.x >> 5) * 2;
   const int x = tx0 + lx, y = ty0 + ly;
   if (x >= width) return;
@@ -86,15 +87,15 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ in,
     float px[12];
     const float* t = tile + HALO * LSTRIDE + HALO;
     if (r == 0) {
-      pixel<site_class<PAT, 0>()>(t, lx + 0, ly, px + 0);
-      pixel<site_class<PAT, 1>()>(t, lx + 1, ly, px + 3);
-      pixel<site_class<PAT, 0>()>(t, lx + 2, ly, px + 6);
-      pixel<site_class<PAT, 1>()>(t, lx + 3, ly, px + 9);
+      pixel<site_class<PAT, 0>(), FULL>(t, lx + 0, ly, px + 0);
+      pixel<site_class<PAT, 1>(), FULL>(t, lx + 1, ly, px + 3);
+      pixel<site_class<PAT, 0>(), FULL>(t, lx + 2, ly, px + 6);
+      pixel<site_class<PAT, 1>(), FULL>(t, lx + 3, ly, px + 9);
     } else {
-      pixel<site_class<PAT, 2>()>(t, lx + 0, ly + 1, px + 0);
-      pixel<site_class<PAT, 3>()>(t, lx + 1, ly + 1, px + 3);
-      pixel<site_class<PAT, 2>()>(t, lx + 2, ly + 1, px + 6);
-      pixel<site_class<PAT, 3>()>(t, lx + 3, ly + 1, px + 9);
+      pixel<site_class<PAT, 2>(), FULL>(t, lx + 0, ly + 1, px + 0);
+      pixel<site_class<PAT, 3>(), FULL>(t, lx + 1, ly + 1, px + 3);
+      pixel<site_class<PAT, 2>(), FULL>(t, lx + 2, ly + 1, px + 6);
+      pixel<site_class<PAT, 3>(), FULL>(t, lx + 3, ly + 1, px + 9);
     }
     const size_t p = (size_t)(y + r) * width + x;
     if (vec_ok) {
@@ -107,6 +108,25 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ in,
       }
     }
   }
+}
+
+template <typename T, int PAT>
+__global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ in, T* __restrict__ out, int width, int height,
+                                                       int vec_ok) {
+  __shared__ float tile[LH * LSTRIDE];
+  __shared__ int votes[4];
+  const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
+  int special = 0;  // a staged sample that is inf or NaN
+  for (int i = threadIdx.x; i < LW * LH; i += 256) {
+    const int r = i / LW, c = i - r * LW;
+    const int gx = min(max(tx0 - HALO + c, 0), width - 1);
+    const int gy = min(max(ty0 - HALO + r, 0), height - 1);
+    const float v = ld(in, (size_t)gy * width + gx);
+    special |= !(fabsf(v) <= 3.402823466e+38f);
+    tile[r * LSTRIDE + c] = v;
+  }
+  if (block_any_sync<4>(special != 0, votes)) bilinear_block<T, PAT, true>(tile, out, width, height, vec_ok, tx0, ty0);
+  else bilinear_block<T, PAT, false>(tile, out, width, height, vec_ok, tx0, ty0);
 }
 
 template <typename T>

@@ -4,10 +4,14 @@
 // green equilibration; PostProcessImpl::process) and csrc/white_balance.cu:10-42,164-183
 // (apply_white_balance).
 //
+// Every kernel here gives the oracle's values on all float32 and binary16 inputs, with NaN at the oracle's positions
+// (tests/test_gpu_demosaic_domain.py); the global equilibration's ratio within its sum-order bound where it is an ordinary quotient.
+//
 // MI355X design
 //  * colour smoothing: 64 x 16 tile per 512-thread workgroup; up to four passes run in one launch on
 //    (R-G, B-G) planes in LDS (zero outside the image, as the reference's halo fill), the median
-//    of nine is 12 min3/med3/max3 instructions, each thread emits 4 pixels as three 16-B stores.
+//    of nine is 12 min3/med3/max3 instructions where the tile's samples are finite and the reference's exchange network
+//    elsewhere (see column_medians below), each thread emits 4 pixels as three 16-B stores.
 //  * global green equilibration: the reference reduces per block, sums the partials with a
 //    torch op and reads two scalars back to the host (postprocess.cu:362-366).  Here a fixed
 //    grid of workgroups writes partial sums, a single-workgroup kernel folds them in a fixed
@@ -19,19 +23,48 @@
 
 namespace {
 
-// Median of nine (reference csrc/reduction.h:93-116 uses a 19-exchange sorting network).  The
-// median is a VALUE, not an order of operations, so any exact selection gives the same bits:
-// with lo/mid/hi = min3/med3/max3 of each row of three,
-//   median9 = med3(max3(lo0, lo1, lo2), med3(mid0, mid1, mid2), min3(hi0, hi1, hi2))
-// -- 12 three-input VALU instructions instead of 57 compare/selects.
+// Median of nine (reference csrc/reduction.h:93-116 uses a 19-exchange sorting network).  For nine values that are totally
+// ordered -- no NaN among them; infinities and ties are fine -- the median is a VALUE, not an order of operations, and any exact
+// selection gives it: with lo/mid/hi = min3/med3/max3 of each row of three,
+//   median  = med3(max3(lo0, lo1, lo2), med3(mid0, mid1, mid2), min3(hi0, hi1, hi2))
+// -- 12 three-input VALU instructions instead of 57 compare/selects.  With a NaN the network is no selection any more: an exchange
+// `a > b` with a NaN operand never swaps, so the NaN stays in its slot, comes out as the result (and the output clamps to 0) if that
+// slot is s[4], and otherwise blocks the exchanges through its slot, so that another order statistic comes out; fminf / fmaxf /
+// med3 drop the NaN instead.  median9_network restates the network, exchange by exchange as the oracle writes it, and the smoothing
+// kernel takes it for the tiles whose staged samples could put a NaN into a difference plane (smoothing_fused_kernel).
+// (The selection form is written out in column_medians.)
 __device__ __forceinline__ float min3f(float a, float b, float c) { return fminf(fminf(a, b), c); }
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 __device__ __forceinline__ float med3f(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
-__device__ __forceinline__ float median9(float s0, float s1, float s2, float s3, float s4, float s5, float s6, float s7, float s8) {
-  const float lo = max3f(min3f(s0, s1, s2), min3f(s3, s4, s5), min3f(s6, s7, s8));
-  const float mid = med3f(med3f(s0, s1, s2), med3f(s3, s4, s5), med3f(s6, s7, s8));
-  const float hi = min3f(max3f(s0, s1, s2), max3f(s3, s4, s5), max3f(s6, s7, s8));
-  return med3f(lo, mid, hi);
+__device__ __forceinline__ void cswap(float& a, float& b) {
+  const float x = a;
+  const bool c = a > b;
+  a = c ? b : a;
+  b = c ? x : b;
+}
+__device__ __forceinline__ float median9_network(float s0, float s1, float s2, float s3, float s4, float s5, float s6, float s7, float s8) {
+  cswap(s1, s2); cswap(s4, s5); cswap(s7, s8);
+  cswap(s0, s1); cswap(s3, s4); cswap(s6, s7);
+  cswap(s1, s2); cswap(s4, s5); cswap(s7, s8);
+  cswap(s0, s3); cswap(s5, s8); cswap(s4, s7);
+  cswap(s3, s6); cswap(s1, s4); cswap(s2, s5);
+  cswap(s4, s7); cswap(s4, s2); cswap(s6, s4);
+  cswap(s4, s2);
+  return s4;
+}
+// The N medians of a column of N + 2 window rows (median k = rows k .. k + 2).  Selection form: the min3 / med3 / max3 of a row are
+// taken once and shared by the up to three windows the row belongs to.
+template <bool NETWORK, int N> __device__ __forceinline__ void column_medians(const float (&w)[N + 2][3], float (&m)[N]) {
+  if constexpr (NETWORK) {
+#pragma unroll
+    for (int k = 0; k < N; k++) m[k] = median9_network(w[k][0], w[k][1], w[k][2], w[k + 1][0], w[k + 1][1], w[k + 1][2], w[k + 2][0], w[k + 2][1], w[k + 2][2]);
+  } else {
+    float lo[N + 2], mid[N + 2], hi[N + 2];
+#pragma unroll
+    for (int j = 0; j < N + 2; j++) { lo[j] = min3f(w[j][0], w[j][1], w[j][2]); mid[j] = med3f(w[j][0], w[j][1], w[j][2]); hi[j] = max3f(w[j][0], w[j][1], w[j][2]); }
+#pragma unroll
+    for (int k = 0; k < N; k++) m[k] = med3f(max3f(lo[k], lo[k + 1], lo[k + 2]), med3f(mid[k], mid[k + 1], mid[k + 2]), min3f(hi[k], hi[k + 1], hi[k + 2]));
+  }
 }
 
 // four consecutive values to storage type T at element index e (16 / 8-byte aligned)
@@ -67,50 +100,13 @@ constexpr int FGR = FLW / 4;           // 18 four-pixel groups per staged row
 static_assert(FGR * FLH <= SNT, "staging: one group per thread");
 static_assert(2 * FPL >= STH * STW * 3, "the last pass's RGB tile fits two planes");
 
-// vec_in / vec_ok: width % 4 == 0 and `in` / `out` aligned to four of their elements (16 bytes fp32, 8 bytes binary16).
-// TI / TO: storage types of `in` and `out` (fp32 between the stages of a call, the caller's type at its two ends)
-template <typename TI, typename TO>
-__global__ __launch_bounds__(SNT) void smoothing_fused_kernel(const TI* __restrict__ in, TO* __restrict__ out, int width, int height, int vec_in, int vec_ok,
-                                                              int passes) {
-  __shared__ __align__(16) float lds[5 * FPL];  // G | DR0 | DB0 | DR1 | DB1
+// The passes of one tile on the staged planes.  NETWORK selects the median (above); everything else is the same code.
+template <bool NETWORK, typename TO>
+__device__ __forceinline__ void smoothing_passes(float* __restrict__ lds, TO* __restrict__ out, int width, int height, int vec_ok, int P, int x0, int y0) {
   float* G = lds;
   auto DR = [&](int k) { return lds + (1 + 2 * k) * FPL; };
   auto DB = [&](int k) { return lds + (2 + 2 * k) * FPL; };
-  const int P = passes;  // 1..FMAXP
-  const int x0 = blockIdx.x * STW, y0 = blockIdx.y * STH;
   const int tid = threadIdx.x;
-  // ---- staging: rows y0 - P .. y0 + STH + P - 1, columns x0 - FCO .. x0 + STW + FCO - 1
-  {
-    const int rh = STH + 2 * P;
-    if (tid < FGR * rh) {
-      const int r = tid / FGR, g4 = tid - r * FGR;
-      const int gy = y0 - P + r, gx = x0 - FCO + 4 * g4;
-      float g[4] = {0.0f, 0.0f, 0.0f, 0.0f}, a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (gy >= 0 && gy < height) {
-        if (vec_in && gx >= 0 && gx + 4 <= width) {  // width % 4 == 0 and a 16-B aligned image: the group is three aligned 16-B loads
-          float v[12];
-          rgb4_io<TI>::load(in, ((size_t)gy * width + gx) >> 2, v);
-#pragma unroll
-          for (int k = 0; k < 4; k++) { g[k] = v[3 * k + 1]; a[k] = v[3 * k] - g[k]; b[k] = v[3 * k + 2] - g[k]; }
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            if (gx + k >= 0 && gx + k < width) {
-              const size_t p = ((size_t)gy * width + gx + k) * 3;
-              g[k] = ld<TI>(in, p + 1); a[k] = ld<TI>(in, p) - g[k]; b[k] = ld<TI>(in, p + 2) - g[k];
-            }
-        }
-      }
-      const int q = (FMAXP - P + r) * FLS + 4 * g4;
-      const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      *reinterpret_cast<float4*>(G + q) = make_float4(g[0], g[1], g[2], g[3]);
-      *reinterpret_cast<float4*>(DR(0) + q) = make_float4(a[0], a[1], a[2], a[3]);
-      *reinterpret_cast<float4*>(DB(0) + q) = make_float4(b[0], b[1], b[2], b[3]);
-      *reinterpret_cast<float4*>(DR(1) + q) = z;  // out-of-image sites stay zero in both buffers
-      *reinterpret_cast<float4*>(DB(1) + q) = z;
-    }
-  }
-  __syncthreads();
   int cur = 0;
   // ---- all passes but the last: region shrinks by one pixel per pass; a thread = one column, RS consecutive rows
   for (int p = 0; p + 1 < P; p++) {
@@ -135,13 +131,15 @@ __global__ __launch_bounds__(SNT) void smoothing_fused_kernel(const TI* __restri
 #pragma unroll
         for (int d = 0; d < 3; d++) { wr[j][d] = pr[j * FLS + d - 1]; wb[j][d] = pb[j * FLS + d - 1]; }
       }
+      float mr[RS], mb[RS];
+      column_medians<NETWORK, RS>(wr, mr);
+      column_medians<NETWORK, RS>(wb, mb);
 #pragma unroll
       for (int k = 0; k < RS; k++) {
         const int r = r0 + k, gy = y0 - FMAXP + r;
         if (RS * sg + k >= ch || gy < 0 || gy >= height) continue;
         const int q = r * FLS + c;
-        const float rm = median9(wr[k][0], wr[k][1], wr[k][2], wr[k + 1][0], wr[k + 1][1], wr[k + 1][2], wr[k + 2][0], wr[k + 2][1], wr[k + 2][2]);
-        const float bm = median9(wb[k][0], wb[k][1], wb[k][2], wb[k + 1][0], wb[k + 1][1], wb[k + 1][2], wb[k + 2][0], wb[k + 2][1], wb[k + 2][2]);
+        const float rm = mr[k], bm = mb[k];
         const float g = G[q];
         const float nr = fmaxf(fmaxf(rm + g, 0.0f), 0.0f), ng = fmaxf(g, 0.0f), nb = fmaxf(fmaxf(bm + g, 0.0f), 0.0f);
         G[q] = ng;  // only this thread reads G[q]
@@ -167,10 +165,12 @@ __global__ __launch_bounds__(SNT) void smoothing_fused_kernel(const TI* __restri
 #pragma unroll
       for (int d = 0; d < 3; d++) { wr[j][d] = pr[j * FLS + d - 1]; wb[j][d] = pb[j * FLS + d - 1]; }
     }
+    float mr[2], mb[2];
+    column_medians<NETWORK, 2>(wr, mr);
+    column_medians<NETWORK, 2>(wb, mb);
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-      const float rm = median9(wr[k][0], wr[k][1], wr[k][2], wr[k + 1][0], wr[k + 1][1], wr[k + 1][2], wr[k + 2][0], wr[k + 2][1], wr[k + 2][2]);
-      const float bm = median9(wb[k][0], wb[k][1], wb[k][2], wb[k + 1][0], wb[k + 1][1], wb[k + 1][2], wb[k + 2][0], wb[k + 2][1], wb[k + 2][2]);
+      const float rm = mr[k], bm = mb[k];
       const float g = G[(r0 + k) * FLS + c];
       float* t = tile + (2 * sg + k) * (3 * STW) + 3 * col;
       t[0] = fmaxf(fmaxf(rm + g, 0.0f), 0.0f);
@@ -191,6 +191,68 @@ __global__ __launch_bounds__(SNT) void smoothing_fused_kernel(const TI* __restri
       }
     }
   }
+}
+
+// vec_in / vec_ok: width % 4 == 0 and `in` / `out` aligned to four of their elements (16 bytes fp32, 8 bytes binary16).
+// TI / TO: storage types of `in` and `out` (fp32 between the stages of a call, the caller's type at its two ends)
+//
+// Which median: a NaN can enter a difference plane of this launch only from a staged pixel whose R - G or B - G is NaN, or whose G
+// is not finite (G = +inf turns max(median + G, 0) - max(G, 0) into inf - inf one pass later).  With every staged G finite and no
+// NaN difference, max(G, 0) stays finite and max(x, 0) - finite is never NaN, whatever overflows: the planes stay totally ordered
+// through all passes and the selection form is exact.  So the workgroup notes such a pixel while staging (one vote per wave
+// through LDS, around the barrier that was there already) and takes the exchange network for the whole tile if there is one -- its bits are the oracle's on every
+// float32 / binary16 input, NaN-displaced selections included; every ordinary tile keeps the 12-instruction form.
+// Cost of the test at 4096 x 3072 on the finite scene, 3 passes, median of 5 x 40 launches, parent -> this kernel:
+//   f32 87.0 -> 91.9 us (+5.6 %), f16 75.0 -> 77.3 us (+3.1 %); the parent's own spread is 0.7 and 1.7 us.  The fast path's
+//   instruction stream behind the vote is the parent's; a __syncthreads_or (three barriers) in its place cost +14 us
+//   (profiles/demosaic_domain_bench.py, profiles/r21/demosaic_domain_bench.txt).
+template <typename TI, typename TO>
+__global__ __launch_bounds__(SNT) void smoothing_fused_kernel(const TI* __restrict__ in, TO* __restrict__ out, int width, int height, int vec_in, int vec_ok,
+                                                              int passes) {
+  __shared__ __align__(16) float lds[5 * FPL];  // G | DR0 | DB0 | DR1 | DB1
+  __shared__ int votes[SNT / 64];
+  float* G = lds;
+  auto DR = [&](int k) { return lds + (1 + 2 * k) * FPL; };
+  auto DB = [&](int k) { return lds + (2 + 2 * k) * FPL; };
+  const int P = passes;  // 1..FMAXP
+  const int x0 = blockIdx.x * STW, y0 = blockIdx.y * STH;
+  const int tid = threadIdx.x;
+  int special = 0;  // a staged pixel that can put a NaN into a difference plane
+  // ---- staging: rows y0 - P .. y0 + STH + P - 1, columns x0 - FCO .. x0 + STW + FCO - 1
+  {
+    const int rh = STH + 2 * P;
+    if (tid < FGR * rh) {
+      const int r = tid / FGR, g4 = tid - r * FGR;
+      const int gy = y0 - P + r, gx = x0 - FCO + 4 * g4;
+      float g[4] = {0.0f, 0.0f, 0.0f, 0.0f}, a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (gy >= 0 && gy < height) {
+        if (vec_in && gx >= 0 && gx + 4 <= width) {  // width % 4 == 0 and a 16-B aligned image: the group is three aligned 16-B loads
+          float v[12];
+          rgb4_io<TI>::load(in, ((size_t)gy * width + gx) >> 2, v);
+#pragma unroll
+          for (int k = 0; k < 4; k++) { g[k] = v[3 * k + 1]; a[k] = v[3 * k] - g[k]; b[k] = v[3 * k + 2] - g[k]; }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            if (gx + k >= 0 && gx + k < width) {
+              const size_t p = ((size_t)gy * width + gx + k) * 3;
+              g[k] = ld<TI>(in, p + 1); a[k] = ld<TI>(in, p) - g[k]; b[k] = ld<TI>(in, p + 2) - g[k];
+            }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) special |= !(fabsf(g[k]) <= 3.402823466e+38f) | (a[k] != a[k]) | (b[k] != b[k]);
+      const int q = (FMAXP - P + r) * FLS + 4 * g4;
+      const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      *reinterpret_cast<float4*>(G + q) = make_float4(g[0], g[1], g[2], g[3]);
+      *reinterpret_cast<float4*>(DR(0) + q) = make_float4(a[0], a[1], a[2], a[3]);
+      *reinterpret_cast<float4*>(DB(0) + q) = make_float4(b[0], b[1], b[2], b[3]);
+      *reinterpret_cast<float4*>(DR(1) + q) = z;  // out-of-image sites stay zero in both buffers
+      *reinterpret_cast<float4*>(DB(1) + q) = z;
+    }
+  }
+  if (block_any_sync<SNT / 64>(special != 0, votes)) smoothing_passes<true, TO>(lds, out, width, height, vec_ok, P, x0, y0);
+  else smoothing_passes<false, TO>(lds, out, width, height, vec_ok, P, x0, y0);
 }
 
 // ---- global green equilibration

@@ -14,7 +14,13 @@
 // HBM traffic is the compulsory 4 + 12 B/px (fp32) instead of ~52 B/px; the intermediate
 // never leaves the CU.  Arithmetic is add/mul/abs/min/max only, same term order as the oracle,
 // so results are bit-exact.  The optional pre-median stays a separate plane-to-plane kernel
-// (its 5x5 cross footprint would double the halo for a feature the presets leave off).
+// (its 5x5 cross footprint would double the halo for a feature the presets leave off); its plane is float32 whatever the
+// storage type, so a binary16 call is the float32 result on the same values rounded ONCE, like every other stage.
+//
+// The oracle's bits over the whole float32 / binary16 domain (tests/test_gpu_demosaic_domain.py): fminf / fmaxf, the `>` selects and
+// the pre-median's exchange sort treat NaN, +-inf, ties and overflowing sums as the C restatement does.
+// Pre-median + fused kernel at 4096 x 3072, median_threshold 1.5, parent (binary16 plane for binary16 storage) -> float32 plane:
+//   f32 129.8 -> 130.0 us (the same kernels), f16 144.4 -> 142.8 us (profiles/r21/demosaic_domain_bench.txt).
 #include "tdk_stencils.h"
 
 namespace {
@@ -38,8 +44,9 @@ __device__ __forceinline__ int pln_at(int r, int c) { return r * GS + (c >> 2) +
 
 // One 64 x 32 tile.  INTERIOR = the tile, its 1-px intermediate ring and its 4-px raw halo stay at least
 // 3 px inside the image: no in-image tests, no 3x3 border-average path.
-template <typename T, bool INTERIOR>
-__device__ __forceinline__ void ppg_tile(const T* __restrict__ src, const T* __restrict__ orig, T* __restrict__ out, int width, int height,
+// TS: the type of the plane the green pass reads -- T (the mosaic itself) or float (the pre-median's plane)
+template <typename T, typename TS, bool INTERIOR>
+__device__ __forceinline__ void ppg_tile(const TS* __restrict__ src, const T* __restrict__ orig, T* __restrict__ out, int width, int height,
                                          uint32_t pattern, int vec_ok, float* __restrict__ raw, float* __restrict__ pr, float* __restrict__ pg,
                                          float* __restrict__ pb, int tx, int ty) {
   const int x0 = tx * TW, y0 = ty * TH;
@@ -81,7 +88,7 @@ __device__ __forceinline__ void ppg_tile(const T* __restrict__ src, const T* __r
         if (!INTERIOR && (gx < 3 || gy < 3 || gx >= width - 3 || gy >= height - 3)) {
           // the 3x3 neighbourhood of a ring pixel lies inside the staged raw tile (4-px halo); without a pre-median the staged
           // plane IS the original mosaic, so the nine samples come from LDS instead of nine global loads per site
-          if (src == orig) v = border_average([&](int xx, int yy) { return raw[raw_at(yy - (y0 - RH), xx - (x0 - RH))]; }, gx, gy, width, height, pattern);
+          if ((const void*)src == (const void*)orig) v = border_average([&](int xx, int yy) { return raw[raw_at(yy - (y0 - RH), xx - (x0 - RH))]; }, gx, gy, width, height, pattern);
           else v = border_average([&](int xx, int yy) { return ld(orig, (size_t)yy * width + xx); }, gx, gy, width, height, pattern);
         } else {
           // raw column c + RH - 1 + d = 2 ci + (cp + RH - 1 + d): half and offset inside it are compile-time per tap
@@ -139,8 +146,8 @@ __device__ __forceinline__ void ppg_tile(const T* __restrict__ src, const T* __r
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(PNT) void ppg_fused(const T* __restrict__ src, const T* __restrict__ orig, T* __restrict__ out, int width,
+template <typename T, typename TS>
+__global__ __launch_bounds__(PNT) void ppg_fused(const TS* __restrict__ src, const T* __restrict__ orig, T* __restrict__ out, int width,
                                                  int height, uint32_t pattern, int vec_ok) {
   __shared__ float raw[RHT * RS];
   __shared__ float pr[GH * GS], pg[GH * GS], pb[GH * GS];
@@ -161,13 +168,13 @@ __global__ __launch_bounds__(PNT) void ppg_fused(const T* __restrict__ src, cons
   }
   const int x0 = tx * TW, y0 = ty * TH;
   const bool interior = x0 >= 8 && y0 >= 8 && x0 + TW + 8 <= width && y0 + TH + 8 <= height;
-  if (interior) ppg_tile<T, true>(src, orig, out, width, height, pattern, vec_ok, raw, pr, pg, pb, tx, ty);
-  else ppg_tile<T, false>(src, orig, out, width, height, pattern, vec_ok, raw, pr, pg, pb, tx, ty);
+  if (interior) ppg_tile<T, TS, true>(src, orig, out, width, height, pattern, vec_ok, raw, pr, pg, pb, tx, ty);
+  else ppg_tile<T, TS, false>(src, orig, out, width, height, pattern, vec_ok, raw, pr, pg, pb, tx, ty);
 }
 
 // reference ppg.cu:21-113; threshold already divided by 100
 template <typename T>
-__global__ __launch_bounds__(256) void pre_median_kernel(const T* __restrict__ in, T* __restrict__ out, int width, int height,
+__global__ __launch_bounds__(256) void pre_median_kernel(const T* __restrict__ in, float* __restrict__ out, int width, int height,
                                                          uint32_t pattern, float threshold) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= width || y >= height) return;
@@ -201,22 +208,22 @@ __global__ __launch_bounds__(256) void pre_median_kernel(const T* __restrict__ i
     const float delta = target - center;
     color = center + fminf(fmaxf(delta, -threshold), threshold);
   }
-  st(out, (size_t)y * width + x, fmaxf(color, 0.0f));
+  out[(size_t)y * width + x] = fmaxf(color, 0.0f);
 }
 
 template <typename T>
 int launch(const void* bayer, void* rgb, void* workspace, int width, int height, uint32_t pattern, float median_threshold, hipStream_t s) {
   const T* in = reinterpret_cast<const T*>(bayer);
-  const T* src = in;
+  const int vec_ok = (width % 4 == 0) && tdk_aligned(rgb, 16);
+  const dim3 grid(tdk_div_up(width, TW) * tdk_div_up(height, TH));
   if (median_threshold > 0.0f) {
-    T* med = reinterpret_cast<T*>(workspace);
+    float* med = reinterpret_cast<float*>(workspace);  // tdk_ppg_workspace_bytes: one float per pixel for every storage type
     TDK_LAUNCH("tdk_ppg(pre_median)", pre_median_kernel<T>, dim3(tdk_div_up(width, 64), tdk_div_up(height, 4)), dim3(256), 0, s, in, med, width, height,
                        pattern, median_threshold / 100.0f);
-    src = med;
+    TDK_LAUNCH("tdk_ppg", (ppg_fused<T, float>), grid, dim3(PNT), 0, s, (const float*)med, in, reinterpret_cast<T*>(rgb), width, height, pattern, vec_ok);
+  } else {
+    TDK_LAUNCH("tdk_ppg", (ppg_fused<T, T>), grid, dim3(PNT), 0, s, in, in, reinterpret_cast<T*>(rgb), width, height, pattern, vec_ok);
   }
-  const int vec_ok = (width % 4 == 0) && tdk_aligned(rgb, 16);
-  TDK_LAUNCH("tdk_ppg", ppg_fused<T>, dim3(tdk_div_up(width, TW) * tdk_div_up(height, TH)), dim3(PNT), 0, s, src, in, reinterpret_cast<T*>(rgb),
-                     width, height, pattern, vec_ok);
   return TDK_OK;
 }
 

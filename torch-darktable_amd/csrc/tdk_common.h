@@ -226,6 +226,19 @@ template <> struct s4_io<uint8_t> {   // one 32-bit access, bytes in ascending a
 };
 
 // wave64 reductions by cross-lane shuffles (all 64 lanes must be active)
+// Workgroup-wide OR of a per-thread predicate with ONE barrier -- the __syncthreads() the caller needs anyway between staging a
+// tile and reading it (__syncthreads_or costs three).  Every wave leaves its vote in its own slot, so the slots need no
+// initialisation; `slots` = NW ints of LDS for a workgroup of NW waves, written once per kernel.  The result is wave-uniform.
+template <int NW> __device__ __forceinline__ bool block_any_sync(bool pred, int* slots) {
+  const int vote = __any(pred);
+  if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = vote;
+  __syncthreads();
+  int r = 0;
+#pragma unroll
+  for (int k = 0; k < NW; k++) r |= slots[k];
+  return __builtin_amdgcn_readfirstlane(r) != 0;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
