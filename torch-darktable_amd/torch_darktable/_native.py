@@ -225,6 +225,15 @@ CA_SIGNATURES = {
                               c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_rawcodec.h, the lossless raw codec (every pointer a device pointer)
+RAWCODEC_SIGNATURES = {
+  'tdk_rawcodec_abi_version': (c_int, []),
+  'tdk_rawcodec_table_bytes': (c_size_t, [c_int, c_int]),
+  'tdk_rawcodec_max_stream_bytes': (c_size_t, [c_int, c_int]),
+  'tdk_rawcodec_encode': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+  'tdk_rawcodec_decode': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -241,6 +250,7 @@ HEADERS = (
   ('tdk_hip_motion.h', MOTION_SIGNATURES, 'tdk_motion_abi_version', 1, 'motion ABI'),
   ('tdk_hip_hdr.h', HDR_SIGNATURES, 'tdk_hdr_abi_version', 1, 'hdr ABI'),
   ('tdk_hip_ca.h', CA_SIGNATURES, 'tdk_ca_abi_version', 1, 'chromatic aberration ABI'),
+  ('tdk_hip_rawcodec.h', RAWCODEC_SIGNATURES, 'tdk_rawcodec_abi_version', 1, 'raw codec ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
@@ -286,6 +296,9 @@ TDK_CA_BILINEAR, TDK_CA_BICUBIC = 0, 1
 TDK_CA_LINEAR, TDK_CA_POLY3 = 0, 1
 TDK_CA_MAX_FRAMES, TDK_CA_SUMS, TDK_CA_MIN_SITES = 16, 17, 16
 TDK_CA_QSCALE, TDK_CA_QMAX = 65535.0, 65535
+# include/tdk_hip_rawcodec.h: the format's constants and the bits of the status of tdk_rawcodec_decode
+TDK_RAWCODEC_FORMAT_VERSION, TDK_RAWCODEC_HEADER_BYTES, TDK_RAWCODEC_SPAN, TDK_RAWCODEC_SEGMENT, TDK_RAWCODEC_MAX_SITES = 1, 32, 64, 512, 1 << 30
+TDK_RAWCODEC_BAD_MAGIC, TDK_RAWCODEC_BAD_SIZE, TDK_RAWCODEC_BAD_TABLES = 1, 2, 4
 
 
 def load() -> C.CDLL:

@@ -25,6 +25,7 @@ from ..hdrmerge import HdrMerge
 from ..highlights import Highlights
 from ..local_contrast import Bilateral
 from ..noiseprofile import NoiseModel
+from ..rawcodec import RawCodec, RawCodecResult
 from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
@@ -45,6 +46,7 @@ class ImageSizeMismatchError(Exception):
         self.image_size = image_size
         self.packed_format = packed_format
         self.padding = padding
+        self.compressed_status: dict[str, torch.Tensor] = {}   # the raw codec's status per frame of the last process_*_compressed call
 
 
 class ImageProcessor:
@@ -398,6 +400,34 @@ class ImageProcessor:
     def process_image_set(self, image_set_bytes: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         """One synchronised set of cameras: shared bounds / metrics (moving-averaged across calls)."""
         return self._process_image_set(image_set_bytes, resized=False)
+
+    def _decompress(self, stream, codec: RawCodec) -> tuple[torch.Tensor, torch.Tensor]:
+        """A TDKR stream (a RawCodecResult or a 1-D uint8 device tensor) -> (the buffer `process` takes: expected_bytes long, the frame in
+        the processor's packed_format, the padding bytes zero; the decoder's status, a 0-dim int32 device tensor)."""
+        if not isinstance(codec, RawCodec):
+            raise TypeError(f'codec must be a RawCodec, got {type(codec).__name__}')
+        if tuple(codec.image_size) != tuple(self.image_size):
+            raise self._mismatch(f'Image size mismatch: the codec is for {codec.image_size}, the processor for {tuple(self.image_size)}. ')
+        data = stream.data if isinstance(stream, RawCodecResult) else stream
+        buffer = torch.empty(self.expected_bytes, dtype=torch.uint8, device=data.device)
+        if self.padding > 0:
+            buffer[buffer.numel() - self.padding:].zero_()
+        return codec.decode(stream, output=self.packed_format, out=buffer, return_status=True)
+
+    def process_compressed(self, stream, image_name: str, codec: RawCodec) -> torch.Tensor:
+        """`process` of a frame that arrives as a lossless TDKR stream (RawCodec.encode): decoded on the device into the packed bytes
+        `process` takes, so every configuration behaves bit for bit as on the packed file.  Nothing waits for the decoder: a corrupt or
+        truncated stream is processed as the frame the decoder leaves of it (zeros in the segments it refuses).  The decoder's status
+        of the call is kept in `compressed_status[image_name]`, a 0-dim int32 device tensor (0, or RawCodec.BAD_* bits), for a caller
+        who wants to look."""
+        return self.process_image_set_compressed({image_name: stream}, codec)[image_name]
+
+    def process_image_set_compressed(self, image_set_streams: dict, codec: RawCodec) -> dict[str, torch.Tensor]:
+        """`process_image_set` of TDKR streams, one codec (one frame size) for the set; `compressed_status` holds the decoder's status
+        of every frame of the call, by name (see process_compressed)."""
+        decoded = {name: self._decompress(stream, codec) for name, stream in image_set_streams.items()}
+        self.compressed_status = {name: status for name, (_, status) in decoded.items()}
+        return self.process_image_set({name: buffer for name, (buffer, _) in decoded.items()})
 
     def process_resized(self, bytes: torch.Tensor, image_name: str) -> torch.Tensor:
         """`process`, scaled to `final_size` (longest edge = settings.resize_width) before the orientation: the result has
