@@ -234,6 +234,14 @@ RAWCODEC_SIGNATURES = {
   'tdk_rawcodec_decode': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_toneeq.h, the tone equalizer (weights: a host pointer to 3 floats; the others device pointers)
+TONEEQ_SIGNATURES = {
+  'tdk_toneeq_abi_version': (c_int, []),
+  'tdk_toneeq_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_toneeq_lds_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_toneeq': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -251,6 +259,7 @@ HEADERS = (
   ('tdk_hip_hdr.h', HDR_SIGNATURES, 'tdk_hdr_abi_version', 1, 'hdr ABI'),
   ('tdk_hip_ca.h', CA_SIGNATURES, 'tdk_ca_abi_version', 1, 'chromatic aberration ABI'),
   ('tdk_hip_rawcodec.h', RAWCODEC_SIGNATURES, 'tdk_rawcodec_abi_version', 1, 'raw codec ABI'),
+  ('tdk_hip_toneeq.h', TONEEQ_SIGNATURES, 'tdk_toneeq_abi_version', 1, 'tone equalizer ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
@@ -299,6 +308,9 @@ TDK_CA_QSCALE, TDK_CA_QMAX = 65535.0, 65535
 # include/tdk_hip_rawcodec.h: the format's constants and the bits of the status of tdk_rawcodec_decode
 TDK_RAWCODEC_FORMAT_VERSION, TDK_RAWCODEC_HEADER_BYTES, TDK_RAWCODEC_SPAN, TDK_RAWCODEC_SEGMENT, TDK_RAWCODEC_MAX_SITES = 1, 32, 64, 512, 1 << 30
 TDK_RAWCODEC_BAD_MAGIC, TDK_RAWCODEC_BAD_SIZE, TDK_RAWCODEC_BAD_TABLES = 1, 2, 4
+# include/tdk_hip_toneeq.h: the gain table (exposures covered, nodes per octave, entries) and the largest radius
+TDK_TONEEQ_EV_MIN, TDK_TONEEQ_EV_MAX, TDK_TONEEQ_STEPS, TDK_TONEEQ_TABLE = -16, 4, 32, 641
+TDK_TONEEQ_MAX_RADIUS = 8
 
 
 def load() -> C.CDLL:

@@ -1,5 +1,5 @@
 """packed raw bytes -> uint8 RGB: decode -> [temporal denoise of the raw mosaic | merge of an exposure bracket (process_bracket)] -> [chromatic aberration] -> [white balance | highlight reconstruction] -> demosaic -> [post-process] ->
-[wavelet chroma denoise, with `noise_model` inside the variance-stabilising transform] -> [colour transform] ->
+[wavelet chroma denoise, with `noise_model` inside the variance-stabilising transform] -> [colour transform] -> [tone equalizer] ->
 normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [sharpen] -> orientation
 (reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
 instead of the minimum and maximum over the set.  `process_resized` / `process_image_set_resized` put the
@@ -30,6 +30,7 @@ from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
 from ..temporal import TemporalDenoise
+from ..toneequal import ToneEqualizer
 from ..wavelet import Wavelet
 from ..white_balance import apply_white_balance
 from .camera_settings import CameraSettings
@@ -149,6 +150,9 @@ class ImageProcessor:
             if not exposure.quantiles:
                 raise ValueError('exposure needs at least one quantile: the bounds are its first and last')
         self.exposure = exposure
+        # dodge and burn by exposure band on every demosaiced frame, behind `color` and in front of the bounds: the property
+        # `tone_equalizer` (every constructor slot is pinned by the test of an earlier stage); None: the reference's chain
+        self._tone_equalizer: ToneEqualizer | None = None
         self._lum_plane: torch.Tensor | None = None  # lightness plane handed from the denoiser to the bilateral stage
         self._ab_plane: torch.Tensor | None = None   # ... and the chroma (a, b) plane of the Lab hand-over
         self.metrics: torch.Tensor | None = None  # moving averages, device-resident
@@ -213,6 +217,20 @@ class ImageProcessor:
     @property
     def final_size(self) -> tuple[int, int]:
         return resize_longest_edge(self.image_size, self.settings.resize_width)
+
+    @property
+    def tone_equalizer(self) -> ToneEqualizer | None:
+        """The tone equalizer run on every demosaiced frame behind `color`, so that bounds and metrics see its result; None: no such stage."""
+        return self._tone_equalizer
+
+    @tone_equalizer.setter
+    def tone_equalizer(self, stage: ToneEqualizer | None) -> None:
+        if stage is not None:
+            if not isinstance(stage, ToneEqualizer):
+                raise TypeError(f'tone_equalizer must be a ToneEqualizer or None, got {type(stage).__name__}')
+            if stage.image_size != tuple(self.image_size):
+                raise ValueError(f'tone_equalizer is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
+        self._tone_equalizer = stage
 
     @property
     def expected_bytes(self) -> int:
@@ -459,6 +477,8 @@ class ImageProcessor:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
         if self.color is not None:
             rgb = [self.color.process(img) for img in rgb]
+        if self._tone_equalizer is not None:
+            rgb = [self._tone_equalizer.process(img) for img in rgb]
         if self.exposure is not None and len(rgb) > self.exposure.max_frames:
             raise ValueError(f'exposure takes {self.exposure.max_frames} frames per call (max_frames), the image set has {len(rgb)}')
         bounds = self.exposure.bounds(rgb) if self.exposure is not None else _tonemap.compute_image_bounds(rgb, stride=8)
