@@ -17,6 +17,7 @@ import kernel_isa
 
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'hdrmerge.hip'
+SHARED = [SOURCE.with_name('tdk_mosaic_tile.h')]
 
 
 @pytest.fixture(scope='module')
@@ -60,5 +61,9 @@ def test_launches_and_nothing_else():
     text = SOURCE.read_text()
     assert text.count('TDK_LAUNCH(') == 1 and text.count('TDK_LAUNCH("tdk_hdr_merge"') == 1   # one templated launcher
     assert 'hipLaunchKernelGGL' not in text and '<<<' not in text
+    for header in SHARED:   # the tile layer the kernel is built from launches nothing
+        shared = header.read_text()
+        assert 'TDK_LAUNCH' not in shared and 'hipLaunchKernelGGL' not in shared and '<<<' not in shared, header.name
+        text += shared
     for call in ('hipMalloc', 'hipMemcpy', 'hipMemset', 'Synchronize', 'atomic'):
         assert call not in text, call

@@ -17,6 +17,7 @@ import kernel_isa
 
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'motion.hip'
+SHARED = [SOURCE.with_name('tdk_mosaic_tile.h'), SOURCE.with_name('tdk_temporal_tile.h')]
 
 
 @pytest.fixture(scope='module')
@@ -76,5 +77,9 @@ def test_launches_and_nothing_else():
     for name in ('"tdk_motion_pyramid"', '"tdk_motion_match"', '"tdk_motion_temporal_denoise(filter)"', '"tdk_motion_temporal_denoise(advance)"'):
         assert text.count(f'TDK_LAUNCH({name}') == 1, name
     assert 'hipLaunchKernelGGL' not in text and '<<<' not in text
+    for header in SHARED:   # the tile layer the compensated filter is built from launches nothing
+        shared = header.read_text()
+        assert 'TDK_LAUNCH' not in shared and 'hipLaunchKernelGGL' not in shared and '<<<' not in shared, header.name
+        text += shared
     for call in ('hipMalloc', 'hipMemcpy', 'hipMemset', 'Synchronize', 'atomic'):
         assert call not in text, call

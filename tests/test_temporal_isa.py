@@ -16,6 +16,7 @@ import kernel_isa
 
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / 'torch-darktable_amd' / 'csrc' / 'temporal.hip'
+SHARED = [SOURCE.with_name('tdk_mosaic_tile.h'), SOURCE.with_name('tdk_temporal_tile.h')]
 
 
 @pytest.fixture(scope='module')
@@ -69,5 +70,9 @@ def test_launches_and_nothing_else():
     assert text.count('TDK_LAUNCH(') == 3   # the filter (one templated launcher), the advance and the reset
     assert text.count('"tdk_temporal_denoise(filter)"') == 1 and text.count('"tdk_temporal_denoise(advance)"') == 1 and text.count('TDK_LAUNCH("tdk_temporal_reset"') == 1
     assert 'hipLaunchKernelGGL' not in text and '<<<' not in text
+    for header in SHARED:   # the tile layer the kernels are built from launches nothing
+        shared = header.read_text()
+        assert 'TDK_LAUNCH' not in shared and 'hipLaunchKernelGGL' not in shared and '<<<' not in shared, header.name
+        text += shared
     for call in ('hipMalloc', 'hipMemcpy', 'hipMemset', 'Synchronize', 'atomic'):
         assert call not in text, call

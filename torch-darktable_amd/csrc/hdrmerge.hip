@@ -1,9 +1,11 @@
 // hdrmerge.hip -- the noise-weighted merge of an exposure bracket of raw mosaics (include/tdk_hip_hdr.h: tdk_hdr_merge, one tile launch).
 //
-// The specification is the head comment of include/tdk_hip_hdr.h.  The storage helpers and the two passes of the window sums are those
-// of temporal.hip, duplicated here so that nothing this file needs can change that file's code.
+// The specification is the head comment of include/tdk_hip_hdr.h.  The storage helpers, the rows of the noise model, the tile geometry
+// with its apron mapping and staged LDS planes, the column sums and the threshold step are those of the temporal filters:
+// tdk_mosaic_tile.h, with a tile of 32 x 32 sites and four sites per lane.  The row sums are that header's too, but written out in the
+// frame loop (the reason stands there).  Steps 0 to 2 and 4 and the arithmetic of a site in a frame are this file's own.
 //
-// hd_merge<TS, TO, R>: a workgroup of 256 lanes owns an output tile of HD_TH = 32 rows of HD_TW = 32 sites.  A lane takes four
+// hd_merge<TS, TO, R>: a workgroup of 256 lanes owns an output tile of 32 rows of 32 sites (HdTile<R>).  A lane takes four
 // consecutive sites of one tile row (the interior) and, the first 20 R + 64 lanes, one unit of four sites of the apron: the R rows above
 // and below and one unit left and right of the tile.  What a lane knows about its sites stays in its registers through the frame loop.
 //   0. every lane finds the shortest and the longest exposure; F lanes write the ratios k_f and one lane the frame addresses into LDS,
@@ -17,37 +19,23 @@
 //      blown or anchored on f is staged as +0.0f), row sums, column sums, then the weight of f at the four interior sites goes into
 //      num and den.
 //   4. out = num / den or R, and the mask byte.
-#include <math.h>
-
 #include "../../include/tdk_hip_hdr.h"
-#include "tdk_frame.h"
+#include "tdk_mosaic_tile.h"
 
 namespace {
 
-constexpr int HD_TW = TDK_HDR_TILE_W, HD_TH = TDK_HDR_TILE_H;
-constexpr int HD_THREADS = 256;
-constexpr int HD_GROUP = 4;                          // sites of a lane in the interior
-constexpr int HD_GROUPS = HD_TW / HD_GROUP;          // lanes of a tile row
-constexpr int HD_SIDE = 4;                           // staged columns on either side of the tile: one unit of four sites
-constexpr int HD_SW = HD_TW + 2 * HD_SIDE;           // sites of a staged row
-constexpr int HD_UNITS = HD_SW / 4;                  // units of four sites of a staged row
-constexpr int HD_MAX_SIZE = 65535;
+template <int R> using HdTile = MtTile<TDK_HDR_TILE_W, TDK_HDR_TILE_H, 4, R>;   // four sites of a lane in the interior
 constexpr int HD_F = TDK_HDR_MAX_FRAMES;
-static_assert(HD_TH * HD_GROUPS == HD_THREADS, "a lane per group of the tile");
-static_assert(HD_SIDE >= 3 + 1, "the apron of the largest radius and the rim of the clip bits");
+static_assert(HdTile<3>::SIDE >= 3 + 1, "the apron of the largest radius and the rim of the clip bits");
 static_assert(HD_F <= 8, "a clip bit per frame in a byte");
 
 template <int R> struct HdLds {
-  alignas(16) float e[(HD_TH + 2 * R) * HD_SW];      // staged: tile and apron
-  alignas(16) float v[(HD_TH + 2 * R) * HD_SW];
-  alignas(16) float re[(HD_TH + 2 * R) * HD_TW];     // row sums of the tile's columns
-  alignas(16) float rv[(HD_TH + 2 * R) * HD_TW];
-  alignas(16) uint32_t clip[(HD_TH + 2 * R + 2) * HD_UNITS];   // a byte per site, four sites a word: one row more on either side
+  typename HdTile<R>::Lds t;                                                   // the staged planes and their row sums
+  alignas(16) uint32_t clip[(HdTile<R>::ROWS + 2) * HdTile<R>::UNITS];         // a byte per site, four sites a word: one row more on either side
   alignas(16) const void* frame[HD_F];
   float k[HD_F];
 };
 static_assert(sizeof(HdLds<3>) <= 64 * 1024, "LDS of the merge launch");
-static_assert(2 * 3 * HD_UNITS + 2 * HD_TH <= HD_THREADS, "a lane per apron unit");
 // the register budget: four waves per SIMD (128 registers); the LDS would admit six workgroups
 constexpr int HD_WAVES = 4;
 
@@ -62,84 +50,6 @@ struct HdArgs {
   float clip, t_hi, inv, c2, v_min;
 };
 
-struct HdRow {
-  float a, b;
-  bool valid;
-};
-
-__device__ __forceinline__ HdRow hd_row(const float* __restrict__ model, int row) {
-  HdRow o;
-  o.valid = model[4 * row + 2] != 0.0f;
-  o.a = o.valid ? model[4 * row] : 1.0f;
-  o.b = o.valid ? model[4 * row + 1] : 0.0f;
-  return o;
-}
-
-// row k of three, field by field: values, not addresses, so that the rows stay in registers
-__device__ __forceinline__ HdRow hd_pick(int k, const HdRow& r0, const HdRow& r1, const HdRow& r2) {
-  HdRow o;
-  o.a = k == 0 ? r0.a : k == 1 ? r1.a : r2.a;
-  o.b = k == 0 ? r0.b : k == 1 ? r1.b : r2.b;
-  o.valid = k == 0 ? r0.valid : k == 1 ? r1.valid : r2.valid;
-  return o;
-}
-
-// ---- storage: M consecutive elements at p, as float32.  One or two 16-byte vectors (8 bytes for four binary16) when p is on such a
-// boundary, per element otherwise.
-template <typename T, int M> __device__ __forceinline__ bool hd_vector_ok(const T* p) {
-  constexpr uintptr_t ALIGN = M * sizeof(T) >= 16 ? 16 : M * sizeof(T);
-  return (reinterpret_cast<uintptr_t>(p) & (ALIGN - 1)) == 0;
-}
-
-template <int M> __device__ __forceinline__ void hd_load(const float* p, float x[M]) {
-#pragma unroll
-  for (int k = 0; k < M / 4; k++) {
-    const float4 u = reinterpret_cast<const float4*>(p)[k];
-    x[4 * k] = u.x, x[4 * k + 1] = u.y, x[4 * k + 2] = u.z, x[4 * k + 3] = u.w;
-  }
-}
-template <int M> __device__ __forceinline__ void hd_load(const __half* p, float x[M]) {
-  uint32_t w[M / 2];
-  if constexpr (M == 8) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    w[0] = u.x, w[1] = u.y, w[2] = u.z, w[3] = u.w;
-  } else {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    w[0] = u.x, w[1] = u.y;
-  }
-#pragma unroll
-  for (int k = 0; k < M; k++) x[k] = __half2float(__ushort_as_half((unsigned short)((w[k / 2] >> (16 * (k % 2))) & 0xffffu)));
-}
-template <int M> __device__ __forceinline__ void hd_store(float* p, const float y[M]) {
-#pragma unroll
-  for (int k = 0; k < M / 4; k++) reinterpret_cast<float4*>(p)[k] = make_float4(y[4 * k], y[4 * k + 1], y[4 * k + 2], y[4 * k + 3]);
-}
-template <int M> __device__ __forceinline__ void hd_store(__half* p, const float y[M]) {
-  uint32_t w[M / 2];
-#pragma unroll
-  for (int k = 0; k < M / 2; k++)
-    w[k] = (uint32_t)__half_as_ushort(__float2half_rn(y[2 * k])) | ((uint32_t)__half_as_ushort(__float2half_rn(y[2 * k + 1])) << 16);
-  if constexpr (M == 8) *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  else *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
-}
-
-// M sites of a frame row from an even column: `live` sites are inside the frame, the others read as 0
-template <typename T, int M> __device__ __forceinline__ void hd_fetch(const T* __restrict__ base, size_t at, int live, float x[M]) {
-  if (live == M && hd_vector_ok<T, M>(base + at)) hd_load<M>(base + at, x);
-  else {
-#pragma unroll
-    for (int m = 0; m < M; m++) x[m] = m < live ? ld<T>(base, at + m) : 0.0f;
-  }
-}
-template <typename T, int M> __device__ __forceinline__ void hd_put(T* __restrict__ base, size_t at, int live, const float y[M]) {
-  if (live == M && hd_vector_ok<T, M>(base + at)) hd_store<M>(base + at, y);
-  else {
-#pragma unroll
-    for (int m = 0; m < M; m++)
-      if (m < live) st<T>(base, at + m, y[m]);
-  }
-}
-
 // byte m of a run of sites packed four to a word
 template <int M> __device__ __forceinline__ uint32_t hd_byte(const uint32_t (&w)[M / 4], int m) { return (w[m / 4] >> (8 * (m % 4))) & 0xffu; }
 
@@ -152,17 +62,17 @@ template <int M> struct HdSites {
 // Step 2 for the M sites from staged unit `unit0` of staged row `srow`; `live` of them are inside the frame, from element `at` on.
 // A site outside the frame is marked blown: it takes no part in any window.
 template <typename TS, int M, int R>
-__device__ __forceinline__ void hd_anchor(const HdLds<R>& lds, int nf, int ref, int lo, int srow, int unit0, size_t at, int live, const HdRow& even,
-                                          const HdRow& odd, float v_min, HdSites<M>& s) {
-  constexpr int W = M / 4;
+__device__ __forceinline__ void hd_anchor(const HdLds<R>& lds, int nf, int ref, int lo, int srow, int unit0, size_t at, int live, const MtRow& even,
+                                          const MtRow& odd, float v_min, HdSites<M>& s) {
+  constexpr int W = M / 4, UNITS = HdTile<R>::UNITS;
   // the OR of the three rows around the sites, one word further on either side (a word outside the plane holds no site of the apron)
   uint32_t col[W + 2];
 #pragma unroll
   for (int k = 0; k < W + 2; k++) {
     const int u = unit0 - 1 + k;
-    const bool in = u >= 0 && u < HD_UNITS;
-    const int c = srow * HD_UNITS + (in ? u : 0);   // plane row srow is the row above staged row srow
-    const uint32_t three = lds.clip[c] | lds.clip[c + HD_UNITS] | lds.clip[c + 2 * HD_UNITS];
+    const bool in = u >= 0 && u < UNITS;
+    const int c = srow * UNITS + (in ? u : 0);   // plane row srow is the row above staged row srow
+    const uint32_t three = lds.clip[c] | lds.clip[c + UNITS] | lds.clip[c + 2 * UNITS];
     col[k] = in ? three : 0u;
   }
 #pragma unroll
@@ -206,7 +116,7 @@ __device__ __forceinline__ void hd_anchor(const HdLds<R>& lds, int nf, int ref, 
 #pragma unroll
   for (int m = 0; m < M; m++) {
     if (m < live) {
-      const HdRow& r = (m & 1) ? odd : even;
+      const MtRow& r = (m & 1) ? odd : even;
       const float Rq = xg[m] / kg[m];
       const float var = fmaxf(r.a * (fmaxf(Rq, 0.0f) * kg[m]) + r.b, v_min);
       s.R[m] = Rq;
@@ -223,13 +133,13 @@ __device__ __forceinline__ void hd_anchor(const HdLds<R>& lds, int nf, int ref, 
 // 1 / (k_f * k_f) are exact and a product with them is the correctly rounded quotient, bit for bit (subnormal results included): the two
 // divisions per site and frame that brackets in whole stops do not need.
 template <int M, bool POW2>
-__device__ __forceinline__ void hd_site(const float x[M], const HdSites<M>& s, int f, float kf, const HdRow& even, const HdRow& odd, float v_min, float r[M],
+__device__ __forceinline__ void hd_site(const float x[M], const HdSites<M>& s, int f, float kf, const MtRow& even, const MtRow& odd, float v_min, float r[M],
                                         float u[M], float e[M], float v[M]) {
   const float kk = kf * kf;
   const float ik = 1.0f / kf, ikk = 1.0f / kk;   // (used when exact)
 #pragma unroll
   for (int m = 0; m < M; m++) {
-    const HdRow& row = (m & 1) ? odd : even;
+    const MtRow& row = (m & 1) ? odd : even;
     r[m] = POW2 ? x[m] * ik : x[m] / kf;
     const float var = fmaxf(row.a * (fmaxf(s.R[m], 0.0f) * kf) + row.b, v_min);
     u[m] = POW2 ? var * ikk : var / kk;
@@ -242,10 +152,12 @@ __device__ __forceinline__ void hd_site(const float x[M], const HdSites<M>& s, i
 }
 
 template <typename TS, typename TO, int R>
-__global__ __launch_bounds__(HD_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
+__global__ __launch_bounds__(MT_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
+  using G = HdTile<R>;
+  constexpr int GROUP = G::GROUP;
   __shared__ HdLds<R> lds;
   const int tid = threadIdx.x;
-  const int x0 = (int)blockIdx.x * HD_TW, y0 = (int)blockIdx.y * HD_TH;
+  const int x0 = (int)blockIdx.x * G::TW, y0 = (int)blockIdx.y * G::TH;
   const int nf = a.nf;
   TO* __restrict__ out = reinterpret_cast<TO*>(a.out);
 
@@ -260,7 +172,7 @@ __global__ __launch_bounds__(HD_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
   }
   const int ref = a.ref < 0 ? hi : a.ref;
   if (tid < nf) lds.k[tid] = a.exposures[tid] / e_lo;
-  if (tid == HD_THREADS - 1) {
+  if (tid == MT_THREADS - 1) {
 #pragma unroll
     for (int f = 0; f < HD_F; f++) lds.frame[f] = a.frames[f];
   }
@@ -270,14 +182,14 @@ __global__ __launch_bounds__(HD_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
   // is clamped into the frame and a site outside it is masked afterwards, so that no load hangs on a condition: the loads of a frame are
   // all in flight before the first comparison, one latency per frame instead of one per unit and frame.
   {
-    constexpr int CLIP_UNITS = (HD_TH + 2 * R + 2) * HD_UNITS, CLIP_PER = (CLIP_UNITS + HD_THREADS - 1) / HD_THREADS;
+    constexpr int CLIP_UNITS = (G::ROWS + 2) * G::UNITS, CLIP_PER = (CLIP_UNITS + MT_THREADS - 1) / MT_THREADS;
     size_t cat[CLIP_PER][4];
     uint32_t inside[CLIP_PER], word[CLIP_PER];
 #pragma unroll
     for (int p = 0; p < CLIP_PER; p++) {
-      const int t = tid + p * HD_THREADS;
-      const int prow = t / HD_UNITS, unit = t % HD_UNITS;
-      const int ci = y0 - (R + 1) + prow, cj = x0 - HD_SIDE + 4 * unit;
+      const int t = tid + p * MT_THREADS;
+      const int prow = t / G::UNITS, unit = t % G::UNITS;
+      const int ci = y0 - (R + 1) + prow, cj = x0 - G::SIDE + 4 * unit;
       const bool row_in = t < CLIP_UNITS && ci >= 0 && ci < a.h;
       const size_t row_at = (size_t)min(max(ci, 0), a.h - 1) * (size_t)a.w;
       inside[p] = word[p] = 0u;
@@ -306,90 +218,77 @@ __global__ __launch_bounds__(HD_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
     }
 #pragma unroll
     for (int p = 0; p < CLIP_PER; p++)
-      if (tid + p * HD_THREADS < CLIP_UNITS) lds.clip[tid + p * HD_THREADS] = word[p];
+      if (tid + p * MT_THREADS < CLIP_UNITS) lds.clip[tid + p * MT_THREADS] = word[p];
   }
   __syncthreads();
 
-  const HdRow r0 = hd_row(a.model, 0), r1 = hd_row(a.model, 1), r2 = hd_row(a.model, 2);
-  // the model rows of the even and the odd columns of frame row i (every unit starts at an even column)
-  auto rows_of = [&](int i, HdRow& even, HdRow& odd) {
-    const uint32_t pair = (a.pattern >> (4u * ((uint32_t)i & 1u))) & 15u;
-    even = hd_pick((int)(pair & 3u), r0, r1, r2);
-    odd = hd_pick((int)(pair >> 2), r0, r1, r2);
-  };
+  const MtRow r0 = mt_row_or_unit(a.model, 0), r1 = mt_row_or_unit(a.model, 1), r2 = mt_row_or_unit(a.model, 2);
 
   // ---- 2. anchors: the interior group of the lane ...
-  const int ty = tid / HD_GROUPS, gx = tid % HD_GROUPS;
-  const int i = y0 + ty, j0 = x0 + HD_GROUP * gx;
-  const int live = i < a.h ? min(max(a.w - j0, 0), HD_GROUP) : 0;
+  const int ty = tid / G::GROUPS, gx = tid % G::GROUPS;
+  const int i = y0 + ty, j0 = x0 + GROUP * gx;
+  const int live = i < a.h ? min(max(a.w - j0, 0), GROUP) : 0;
   const size_t at = (size_t)i * (size_t)a.w + (size_t)j0;   // (not formed into an address unless live > 0)
-  HdRow even, odd;
-  rows_of(i, even, odd);
-  HdSites<HD_GROUP> in;
-  hd_anchor<TS, HD_GROUP, R>(lds, nf, ref, lo, ty + R, (HD_SIDE + HD_GROUP * gx) / 4, at, live, even, odd, a.v_min, in);
+  MtRow even, odd;
+  mt_rows_of(a.pattern, i, r0, r1, r2, even, odd);
+  HdSites<GROUP> in;
+  hd_anchor<TS, GROUP, R>(lds, nf, ref, lo, ty + R, (G::SIDE + GROUP * gx) / 4, at, live, even, odd, a.v_min, in);
 
   // ... and its apron unit: R rows above, R rows below (whole staged rows), one unit left and right of each tile row
-  const bool apron = tid < 2 * R * HD_UNITS + 2 * HD_TH;
+  const bool apron = tid < G::APRON;
   int srow = 0, unit = 0, alive = 0;
   size_t aat = 0;
-  HdRow aeven = even, aodd = odd;
+  MtRow aeven = even, aodd = odd;
   HdSites<4> ap;
   if (apron) {
-    if (tid < 2 * R * HD_UNITS) {
-      const int band = tid / (R * HD_UNITS), u = tid - band * (R * HD_UNITS);
-      srow = band * (R + HD_TH) + u / HD_UNITS;
-      unit = u % HD_UNITS;
-    } else {
-      const int u = tid - 2 * R * HD_UNITS;
-      srow = R + (u >> 1);
-      unit = (u & 1) ? HD_UNITS - 1 : 0;
-    }
-    const int ai = y0 - R + srow, aj = x0 - HD_SIDE + 4 * unit;
+    G::apron_unit(tid, srow, unit);
+    const int ai = y0 - R + srow, aj = x0 - G::SIDE + 4 * unit;
     alive = (ai >= 0 && ai < a.h && aj >= 0) ? min(max(a.w - aj, 0), 4) : 0;
     aat = (size_t)max(ai, 0) * (size_t)a.w + (size_t)max(aj, 0);   // (not formed into an address unless alive > 0)
-    rows_of(ai, aeven, aodd);
+    mt_rows_of(a.pattern, ai, r0, r1, r2, aeven, aodd);
     hd_anchor<TS, 4, R>(lds, nf, ref, lo, srow, unit, aat, alive, aeven, aodd, a.v_min, ap);
   }
 
   // ---- 3. the frames
-  float num[HD_GROUP], den[HD_GROUP];
-  uint32_t count[HD_GROUP / 4] = {};
+  float num[GROUP], den[GROUP];
+  uint32_t count[GROUP / 4] = {};
 #pragma unroll
-  for (int m = 0; m < HD_GROUP; m++) num[m] = den[m] = 0.0f;
+  for (int m = 0; m < GROUP; m++) num[m] = den[m] = 0.0f;
 #pragma unroll 1
   for (int f = 0; f < nf; f++) {
     const float kf = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lds.k[f])));   // the same value in every lane: a scalar
     const bool pow2 = (__float_as_uint(kf) & 0x007fffffu) == 0u && kf >= 1.0f && kf <= 0x1p60f;
     const TS* __restrict__ src = reinterpret_cast<const TS*>(lds.frame[f]);
-    float r[HD_GROUP], u[HD_GROUP];
+    float r[GROUP], u[GROUP];
     {
-      float x[HD_GROUP], e[HD_GROUP], v[HD_GROUP];
+      float x[GROUP], e[GROUP], v[GROUP];
 #pragma unroll
-      for (int m = 0; m < HD_GROUP; m++) x[m] = 0.0f;
-      if (live > 0) hd_fetch<TS, HD_GROUP>(src, at, live, x);
-      if (pow2) hd_site<HD_GROUP, true>(x, in, f, kf, even, odd, a.v_min, r, u, e, v);
-      else hd_site<HD_GROUP, false>(x, in, f, kf, even, odd, a.v_min, r, u, e, v);
-      const int to = (ty + R) * HD_SW + HD_SIDE + HD_GROUP * gx;
-      hd_store<HD_GROUP>(lds.e + to, e);
-      hd_store<HD_GROUP>(lds.v + to, v);
+      for (int m = 0; m < GROUP; m++) x[m] = 0.0f;
+      if (live > 0) mt_fetch<TS, GROUP>(src, (int64_t)at, 0, live, x);
+      if (pow2) hd_site<GROUP, true>(x, in, f, kf, even, odd, a.v_min, r, u, e, v);
+      else hd_site<GROUP, false>(x, in, f, kf, even, odd, a.v_min, r, u, e, v);
+      mt_store<GROUP>(lds.t.e + G::staged(ty, gx), e);
+      mt_store<GROUP>(lds.t.v + G::staged(ty, gx), v);
     }
     if (apron) {
       float ax[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ar[4], au[4], e[4], v[4];
-      if (alive > 0) hd_fetch<TS, 4>(src, aat, alive, ax);
+      if (alive > 0) mt_fetch<TS, 4>(src, (int64_t)aat, 0, alive, ax);
       if (pow2) hd_site<4, true>(ax, ap, f, kf, aeven, aodd, a.v_min, ar, au, e, v);
       else hd_site<4, false>(ax, ap, f, kf, aeven, aodd, a.v_min, ar, au, e, v);
-      hd_store<4>(lds.e + srow * HD_SW + 4 * unit, e);
-      hd_store<4>(lds.v + srow * HD_SW + 4 * unit, v);
+      mt_store<4>(lds.t.e + srow * G::SW + 4 * unit, e);
+      mt_store<4>(lds.t.v + srow * G::SW + 4 * unit, v);
     }
     __syncthreads();
 
-    // row sums: four columns of a staged row per step
+    // row sums: mt_row_sums of tdk_mosaic_tile.h, written out.  Behind any call, a local lambda included, the compiler builds this kernel
+    // otherwise: the selects of hd_site become branches, 56 to 62 instructions more per instantiation, and the binary16 rows of
+    // profiles/hdrmerge_bench.py take 1 to 2 % longer (profiles/r23/tile_layer_bench.txt).
 #pragma unroll 1
-    for (int t = tid; t < (HD_TH + 2 * R) * (HD_TW / 4); t += HD_THREADS) {
-      const int rrow = t / (HD_TW / 4), cu = t % (HD_TW / 4);
+    for (int t = tid; t < G::ROWS * (G::TW / 4); t += MT_THREADS) {
+      const int rrow = t / (G::TW / 4), cu = t % (G::TW / 4);
       float we[12], wv[12];
-      hd_load<12>(lds.e + rrow * HD_SW + 4 * cu, we);   // staged columns 4 cu .. 4 cu + 11: tile columns 4 cu - 4 .. 4 cu + 7
-      hd_load<12>(lds.v + rrow * HD_SW + 4 * cu, wv);
+      mt_load<12>(lds.t.e + rrow * G::SW + 4 * cu, we);   // staged columns 4 cu .. 4 cu + 11: tile columns 4 cu - 4 .. 4 cu + 7
+      mt_load<12>(lds.t.v + rrow * G::SW + 4 * cu, wv);
       float se[4], sv[4];
 #pragma unroll
       for (int m = 0; m < 4; m++) {
@@ -398,36 +297,25 @@ __global__ __launch_bounds__(HD_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
         for (int k = -R; k <= R; k++) e += we[4 + m + k], v += wv[4 + m + k];
         se[m] = e, sv[m] = v;
       }
-      hd_store<4>(lds.re + rrow * HD_TW + 4 * cu, se);
-      hd_store<4>(lds.rv + rrow * HD_TW + 4 * cu, sv);
+      mt_store<4>(lds.t.re + rrow * G::TW + 4 * cu, se);
+      mt_store<4>(lds.t.rv + rrow * G::TW + 4 * cu, sv);
     }
     __syncthreads();
 
     // column sums and the weight of frame f
     if (live > 0) {
-      float E[HD_GROUP], V[HD_GROUP];
+      float E[GROUP], V[GROUP];
+      mt_column_sums<G>(lds.t, ty, gx, E, V);
+      float e[GROUP], v[GROUP];   // of the lane's own sites, as staged
+      mt_load<GROUP>(lds.t.e + G::staged(ty, gx), e);
+      mt_load<GROUP>(lds.t.v + G::staged(ty, gx), v);
 #pragma unroll
-      for (int m = 0; m < HD_GROUP; m++) E[m] = V[m] = 0.0f;
-#pragma unroll 1
-      for (int dr = 0; dr <= 2 * R; dr++) {
-        float pe[HD_GROUP], pv[HD_GROUP];
-        hd_load<HD_GROUP>(lds.re + (ty + dr) * HD_TW + HD_GROUP * gx, pe);
-        hd_load<HD_GROUP>(lds.rv + (ty + dr) * HD_TW + HD_GROUP * gx, pv);
-#pragma unroll
-        for (int m = 0; m < HD_GROUP; m++) E[m] += pe[m], V[m] += pv[m];
-      }
-      float e[HD_GROUP], v[HD_GROUP];   // of the lane's own sites, as staged
-      hd_load<HD_GROUP>(lds.e + (ty + R) * HD_SW + HD_SIDE + HD_GROUP * gx, e);
-      hd_load<HD_GROUP>(lds.v + (ty + R) * HD_SW + HD_SIDE + HD_GROUP * gx, v);
-#pragma unroll
-      for (int m = 0; m < HD_GROUP; m++) {
-        const HdRow& row = (m & 1) ? odd : even;
-        const uint32_t meta = hd_byte<HD_GROUP>(in.meta, m);
-        const float t = E[m] / V[m];
-        float s = fminf(fmaxf((a.t_hi - t) * a.inv, 0.0f), 1.0f);
-        if (e[m] > a.c2 * v[m]) s = 0.0f;
+      for (int m = 0; m < GROUP; m++) {
+        const MtRow& row = (m & 1) ? odd : even;
+        const uint32_t meta = hd_byte<GROUP>(in.meta, m);
+        float s = mt_similarity(E[m], V[m], e[m], v[m], a.t_hi, a.inv, a.c2);
         if (!row.valid || (int)(meta & 7u) == f) s = 1.0f;
-        const bool sat = ((hd_byte<HD_GROUP>(in.sat, m) >> f) & 1u) != 0u;
+        const bool sat = ((hd_byte<GROUP>(in.sat, m) >> f) & 1u) != 0u;
         const float w = sat ? 0.0f : s / u[m];
         if (w > 0.0f) {
           num[m] += w * r[m];
@@ -442,41 +330,32 @@ __global__ __launch_bounds__(HD_THREADS, HD_WAVES) void hd_merge(HdArgs a) {
 
   // ---- 4. the result
   if (live > 0) {
-    float y[HD_GROUP];
+    float y[GROUP];
 #pragma unroll
-    for (int m = 0; m < HD_GROUP; m++) y[m] = den[m] > 0.0f ? num[m] / den[m] : in.R[m];
-    hd_put<TO, HD_GROUP>(out, at, live, y);
+    for (int m = 0; m < GROUP; m++) y[m] = den[m] > 0.0f ? num[m] / den[m] : in.R[m];
+    mt_put<TO, GROUP>(out, at, live, y);
     if (a.mask) {
-      static_assert(HD_GROUP == 4, "the mask bytes of a lane are one word");
+      static_assert(GROUP == 4, "the mask bytes of a lane are one word");
       const uint32_t bytes = in.meta[0] | (count[0] << 4);
       unsigned char* p = a.mask + at;
-      if (live == HD_GROUP && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) *reinterpret_cast<uint32_t*>(p) = bytes;
+      if (live == GROUP && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) *reinterpret_cast<uint32_t*>(p) = bytes;
       else {
 #pragma unroll
-        for (int m = 0; m < HD_GROUP; m++)
+        for (int m = 0; m < GROUP; m++)
           if (m < live) p[m] = (unsigned char)((bytes >> (8 * m)) & 0xffu);
       }
     }
   }
 }
 
-bool hd_pattern_ok(uint32_t pattern) {
-  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
-}
-bool hd_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
-
 template <typename TS, typename TO, int R> int hd_launch(const HdArgs& a, hipStream_t st) {
-  const dim3 grid((unsigned)tdk_div_up(a.w, HD_TW), (unsigned)tdk_div_up(a.h, HD_TH)), block(HD_THREADS);
+  const dim3 grid((unsigned)tdk_div_up(a.w, HdTile<R>::TW), (unsigned)tdk_div_up(a.h, HdTile<R>::TH)), block(MT_THREADS);
   TDK_LAUNCH("tdk_hdr_merge", (hd_merge<TS, TO, R>), grid, block, 0, st, a);
   return TDK_OK;
 }
 
 template <typename TS, typename TO> int hd_launch_radius(const HdArgs& a, int radius, hipStream_t st) {
   return radius == 2 ? hd_launch<TS, TO, 2>(a, st) : hd_launch<TS, TO, 3>(a, st);
-}
-
-template <typename TS> int hd_launch_out(const HdArgs& a, int out_dtype, int radius, hipStream_t st) {
-  return out_dtype == TDK_F32 ? hd_launch_radius<TS, float>(a, radius, st) : hd_launch_radius<TS, __half>(a, radius, st);
 }
 
 }  // namespace
@@ -492,17 +371,12 @@ TDK_EXPORT int tdk_hdr_merge(const void* const* frames, int num_frames, int src_
   TDK_REQUIRE(frames && out && exposures && model, "%s: null pointer (frames, out, exposures or model)", who);
   TDK_REQUIRE(num_frames >= 2 && num_frames <= HD_F, "%s: num_frames must be 2..%d, got %d", who, HD_F, num_frames);
   for (int f = 0; f < num_frames; f++) TDK_REQUIRE(frames[f], "%s: null pointer (frame %d)", who, f);
-  TDK_REQUIRE(hd_dtype_ok(src_dtype) && hd_dtype_ok(out_dtype), "%s: unsupported dtype tags %d -> %d", who, src_dtype, out_dtype);
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= HD_MAX_SIZE && height <= HD_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, HD_MAX_SIZE);
-  TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
-  TDK_REQUIRE(hd_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
-  TDK_REQUIRE(radius == 2 || radius == 3, "%s: radius must be 2 or 3, got %d", who, radius);
+  TDK_REQUIRE(mt_dtype_ok(src_dtype) && mt_dtype_ok(out_dtype), "%s: unsupported dtype tags %d -> %d", who, src_dtype, out_dtype);
+  if (const int rc = mt_check_mosaic(who, width, height, pattern, radius)) return rc;
   TDK_REQUIRE(ref >= -1 && ref < num_frames, "%s: ref must be -1 or a frame index below %d, got %d", who, num_frames, ref);
   TDK_REQUIRE(isfinite(clip) && clip > 0.0f, "%s: clip must be finite and > 0", who);
-  const float inv = 1.0f / (t_hi - t_lo);
-  TDK_REQUIRE(isfinite(t_lo) && isfinite(t_hi) && t_lo > 0.0f && t_hi > t_lo && isfinite(inv),
-              "%s: the thresholds need 0 < t_lo < t_hi, finite, with a finite 1 / (t_hi - t_lo)", who);
-  TDK_REQUIRE(pixel_c2 > 0.0f, "%s: pixel_c2 must be > 0 (+inf turns the per-site test off)", who);
+  float inv;
+  if (const int rc = mt_check_thresholds(who, t_lo, t_hi, pixel_c2, inv)) return rc;
   TDK_REQUIRE(isfinite(v_min) && v_min > 0.0f, "%s: v_min must be finite and > 0", who);
   const size_t sites = (size_t)width * (size_t)height;
   const size_t src_bytes = sites * tdk_dtype_bytes(src_dtype), out_bytes = sites * tdk_dtype_bytes(out_dtype);
@@ -521,5 +395,6 @@ TDK_EXPORT int tdk_hdr_merge(const void* const* frames, int num_frames, int src_
   a.nf = num_frames, a.ref = ref, a.w = width, a.h = height, a.pattern = pattern;
   a.clip = clip, a.t_hi = t_hi, a.inv = inv, a.c2 = pixel_c2, a.v_min = v_min;
   hipStream_t st = tdk_stream(stream);
-  return src_dtype == TDK_F32 ? hd_launch_out<float>(a, out_dtype, radius, st) : hd_launch_out<__half>(a, out_dtype, radius, st);
+  TDK_DISPATCH_DTYPE(src_dtype, TS, TDK_DISPATCH_DTYPE(out_dtype, TO, return hd_launch_radius<TS, TO>(a, radius, st)));
+  return TDK_OK;
 }
