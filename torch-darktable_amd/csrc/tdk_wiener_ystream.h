@@ -25,6 +25,8 @@
 // issued at the top of a step, consumed at its end), so no wave waits on HBM.
 #pragma once
 
+#include "tdk_wiener_interior.h"
+
 namespace ys {
 
 #if defined(TDK_EXPERIMENTS) && defined(TDK_YS_TIMING)
@@ -42,9 +44,7 @@ __device__ unsigned long long g_ys_wg_times[2 * 2048];  // [2 b], [2 b + 1]: wal
 #define YS_ABLATE(n) false
 #endif
 
-constexpr int K = 32, S = 8, NPC = 8;     // tile size, hop, tile PAIRS per strip
-constexpr int NTC = 2 * NPC;              // tile columns per strip (Geom::G)
-constexpr int SW = NTC * S + K - S;       // samples per strip row: 152
+// K = 32, S = 8, NPC = 8, NTC = 16, SW = 152, GRP_PER_ROW = 38, GRP_PER_WAVE = 76: tdk_wiener_interior.h
 constexpr int PITCH = 68;                 // floats per LDS row of 32 complex values (+4: conflict-free 16-B row accesses)
 constexpr int BUF = 64 * PITCH;           // one hand-over block: 8 block rows x 8 tile pairs
 // floats per LDS row of the staging block.  The forward row stage reads it as ds_read_b128 at row * PP + 16 * pair + k; a
@@ -55,8 +55,6 @@ constexpr int BUF = 64 * PITCH;           // one hand-over block: 8 block rows x
 // (profiles/r04/experiments/lds_conflicts.txt); 156 is conflict-free.
 constexpr int PP = SW + 4;
 static_assert((PP / 4) % 2 == 1 && PP % 4 == 0, "staging pitch: odd number of 16-byte slots");
-constexpr int GRP_PER_ROW = SW / 4;       // 16-B groups per staged row: 38
-constexpr int GRP_PER_WAVE = 8 * GRP_PER_ROW / 4;  // 76
 
 struct YParams {
   float whr[32], whi[32];  // FFT of the analysis window wf, natural kx order
@@ -229,43 +227,47 @@ template <> struct RawRgb4<__half> {
 // values compute_log_luminance (color.hip, lum_extract_vec4) would have written to a plane first (reference
 // denoise.py:54-56).  The conversion is done by the two waves of a step that run no row stage, in the time they
 // would otherwise wait at the barrier for the two that do.
-template <typename T, bool LUM>
-__global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ img, float* __restrict__ slabs, int W, int H, int C, int chan0, int vec_ok, Geom g,
-                                                         const float* __restrict__ sigmas, YParams yp, size_t plane_stride, float lum_eps) {
-  __shared__ Smem sm;
-#if defined(TDK_EXPERIMENTS) && defined(TDK_YS_TIMING)
-  if (threadIdx.x == 0 && blockIdx.x < 2048u) g_ys_wg_times[2 * blockIdx.x] = wall_clock64();
-#endif
-  int chan = chan0;
+// One kernel holds two bodies of the round loop: the general one, and the interior body (IN) for the workgroups clear of every
+// frame edge (the rule, the launch order and a lane's staging share: tdk_wiener_interior.h).
+// The round loop of one workgroup.  IN: the interior body (see above); it exists for the planar instantiation only (LUM = false).
+template <typename T, bool LUM, bool IN>
+__device__ __forceinline__ void ystream_body(Smem& sm, const T* __restrict__ base, float* __restrict__ slab, int W, int H, int C, int chan, int vec_ok, const Geom& g, int gx,
+                                             int gy, float sig2, const YParams& yp, float lum_eps) {
+  static_assert(!(IN && LUM), "the interior body reads a plane");
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int ngroups = g.ngx * g.ngy;
-  const int plane = blockIdx.x / ngroups, gin = blockIdx.x - plane * ngroups;
-  const int gy = gin / g.ngx, gx = gin - gy * g.ngx;
-  const float sigma = sigmas[chan + plane];
-  if (C == 3) chan += plane;  // interleaved input: group set p works on channel p of the same image
-  const float sig2 = sigma * sigma;
-  const T* base = img + (size_t)plane * plane_stride;
+  const int uw = __builtin_amdgcn_readfirstlane(wave);  // the same number where the compiler should see that it is wave-uniform
   const int t0 = gy * g.TR, t1 = min(t0 + g.TR, g.nty);
   const int NB = t1 - t0 + 3;                 // 8-row blocks this strip segment reads = blocks its slab holds
   const int px0 = (g.jmin + gx * NTC) * S;    // image x of strip sample 0
   // samples beyond the last active tile of the strip are never used (and may lie beyond one reflection of the frame)
   const int sx_lim = S * min(g.ntx - gx * NTC, NTC) + K - S;
-  float* slab = slabs + (size_t)blockIdx.x * (size_t)(g.RSY * g.RSXP);
 
   // column-stage coordinates: a 32-lane slot per tile pair, lane = kx (partner bin -kx in lane ^ 1)
   const int slot = lane >> 5, l = lane & 31, yc = 2 * wave + slot;
   const int kx = (l == 0) ? 0 : (l == 1) ? K / 2 : (l & 1) ? K - (l >> 1) : (l >> 1);  // == lane_freq(l, K)
-  const bool ya = gx * NTC + 2 * yc < g.ntx, yb = gx * NTC + 2 * yc + 1 < g.ntx;
+  const bool ya = IN || gx * NTC + 2 * yc < g.ntx, yb = IN || gx * NTC + 2 * yc + 1 < g.ntx;
+  // a wave whose two tile pairs both lie beyond the strip's last tile (the last strip of a frame) has no column stage to run: its
+  // windows, carries and results are all zero, and the columns they would reach lie beyond the frame.  It still stages samples,
+  // runs its row stage and hands zeros to the inverse row stage.
+  const bool col_idle = !IN && gx * NTC + 4 * uw >= g.ntx;
   const float whr = yp.whr[kx], whi = yp.whi[kx];
   const int col_off = 2 * yc * PITCH + 2 * kx;  // this lane's element of block row 0 of its tile pair in a hand-over block
   // row-stage coordinates: lane = row_of(xc, xr)
   const int xr = (lane & 1) + 2 * (lane >> 4), xc = (lane >> 1) & 7;
-  const bool xa = gx * NTC + 2 * xc < g.ntx, xb = gx * NTC + 2 * xc + 1 < g.ntx;
-  // staging coordinates: this wave's 76 groups of 4 samples of an 8 x 152 block (lanes < 12 take a second group)
-  const int sg0 = GRP_PER_WAVE * wave + lane, sg1 = sg0 + 64;
-  const bool has1 = lane < GRP_PER_WAVE - 64;
-  const int so0 = (sg0 / GRP_PER_ROW) * PP + 4 * (sg0 % GRP_PER_ROW), so1 = (sg1 / GRP_PER_ROW) * PP + 4 * (sg1 % GRP_PER_ROW);  // their places in the staging block
+  const bool xa = IN || gx * NTC + 2 * xc < g.ntx, xb = IN || gx * NTC + 2 * xc + 1 < g.ntx;
+  // staging coordinates: this wave's 76 groups of 4 samples of an 8 x 152 block = block rows 2 wave and 2 wave + 1 (lanes < 12
+  // take a second group).  Group 0 lies in the upper of the two rows for lanes >= 38, group 1 always.
+  const StageLane sl = stage_lane(lane);
+  const bool hi0 = sl.hi0, has1 = sl.has1;
+  const int col0 = sl.col0, col1 = sl.col1;  // strip columns of the two groups
+  const int so0 = (2 * wave + (hi0 ? 1 : 0)) * PP + col0, so1 = (2 * wave + 1) * PP + col1;  // their places in the staging block
   const bool vec = vec_ok && C == 1;
+  // general body: the groups that lie in the frame and take one vector load (the same for every block of the segment)
+  const bool in0 = vec && px0 + col0 >= 0 && px0 + col0 + 4 <= W, in1 = vec && px0 + col1 >= 0 && px0 + col1 + 4 <= W;
+  // interior body: one row pointer per wave (block row 2 wave of the block to load next, strip sample 0), advanced by 8 rows per
+  // block, and the two groups' constant offsets from it
+  const T* rowp = base + ((size_t)(unsigned)(IN ? S * (t0 + g.jmin) + 2 * uw : 0) * (unsigned)W + (unsigned)(IN ? px0 : 0));
+  const unsigned off0 = interior_off0(sl, W), off1 = interior_off1(sl, W);
 
   v2f win[32];    // R[y][kx] of the current window (tile-relative row y), {re, im} register pairs
   v2f carry[24];  // carried (unfinished) rows of the overlap-add across tile rows, tile-relative
@@ -278,18 +280,14 @@ __global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ i
   // of an in-frame group at the top of a step; a group that touches the frame edge (reflected single samples, or nothing
   // beyond the last active tile) is read by fetch_edge() at the bottom instead.  Keeping the two apart matters: loads into the
   // same registers from both paths would make the compiler drain vmcnt between them -- behind the step's slab stores.
-  auto fetch = [&](int grp, int q, Raw4<T>& raw) -> bool {
-    const int brow = grp / GRP_PER_ROW, x = px0 + 4 * (grp - brow * GRP_PER_ROW);
-    if (!(vec && x >= 0 && x + 4 <= W)) return false;
-    raw.load4(base + (size_t)(unsigned)reflect_index(8 * q + brow + g.jmin * S, H) * (unsigned)W + x);
-    return true;
-  };
-  auto fetch_edge = [&](int grp, int q) -> float4 {
-    const int brow = grp / GRP_PER_ROW, col = 4 * (grp - brow * GRP_PER_ROW);
-    const T* rowp = base + (size_t)reflect_index(8 * q + brow + g.jmin * S, H) * W * C;
+  // The image rows are those of block rows 2 wave (lo) and 2 wave + 1 (hi) of block q, reflected once per block row on the scalar
+  // unit; the group's column and whether it lies in the frame are the lane constants above.
+  auto fetch = [&](int row, int col, Raw4<T>& raw) { raw.load4(base + ((size_t)(unsigned)row * (unsigned)W + (unsigned)(px0 + col))); };
+  auto fetch_edge = [&](int row, int col) -> float4 {
+    const T* rp = base + (size_t)row * W * C;
     float v[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) v[j] = (col + j < sx_lim) ? ld(rowp, (size_t)reflect_index(px0 + col + j, W) * C + chan) : 0.0f;
+    for (int j = 0; j < 4; j++) v[j] = (col + j < sx_lim) ? ld(rp, (size_t)reflect_index(px0 + col + j, W) * C + chan) : 0.0f;
     return make_float4(v[0], v[1], v[2], v[3]);
   };
   auto emit = [&](float* dst, const v2f (&o)[8]) {
@@ -395,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ i
         asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(s1), "+v"(s2));
         if ((lane & 1) == 0 && lane < 32) sm.meta[bb & 7][2 * xc + (lane >> 4)] = s1 + s2;
         v2f z[K];
-        if (__builtin_amdgcn_ballot_w64(!(xa && xb)) == 0) {  // every tile of the strip exists (all strips but the last one)
+        if (IN || __builtin_amdgcn_ballot_w64(!(xa && xb)) == 0) {  // every tile of the strip exists (all strips but the last one)
 #pragma unroll
           for (int k = 0; k < K; k++) z[k] = v2f{w[k] * WindowK<32>::w[k], w[k + S] * WindowK<32>::w[k]};
         } else {
@@ -424,11 +422,20 @@ __global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ i
       const int qs = 2 * it + blk;
       Raw4<T> st0, st1;
       RawRgb4<T> px[3];
-      bool pk0 = false, pk1 = false, pkx[3] = {false, false, false};
-      if constexpr (!LUM) {
+      bool pkx[3] = {false, false, false};
+      int r_lo = 0, r_hi = 0;  // general body: the image rows of this wave's two block rows of block qs (wave-uniform)
+      if constexpr (IN) {
         if (qs < NB) {
-          pk0 = fetch(sg0, t0 + qs, st0);
-          if (has1) pk1 = fetch(sg1, t0 + qs, st1);
+          st0.load4(rowp + off0);
+          if (has1) st1.load4(rowp + off1);
+          rowp += (size_t)(unsigned)(S * W);
+        }
+      } else if constexpr (!LUM) {
+        if (qs < NB) {
+          r_lo = reflect_index(S * (t0 + qs + g.jmin) + 2 * uw, H);
+          r_hi = reflect_index(S * (t0 + qs + g.jmin) + 2 * uw + 1, H);
+          if (in0) fetch(hi0 ? r_hi : r_lo, col0, st0);
+          if (has1 && in1) fetch(r_hi, col1, st1);
         }
       } else {
         if (qs < NB && sblk == blk) {
@@ -446,7 +453,12 @@ __global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ i
         }
       }
       YS_MARK(0);  // staging loads issued
-      if (b >= 0 && b < NB) {
+      if (col_idle) {
+        if (b >= 3 && b < NB + 3) {  // the rounds in which the column stage hands a block to the inverse row stage
+          const v2f o[8] = {};
+          emit(sm.inv[blk] + col_off, o);
+        }
+      } else if (b >= 0 && b < NB) {
         // the window moves down one block: rows 8 .. 31 become rows 0 .. 23 (24 pair moves: cheaper than what the compiler
         // makes of a code variant per window phase), the arriving block becomes rows 24 .. 31
 #pragma unroll
@@ -501,11 +513,17 @@ __global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ i
       YS_MARK(1);  // column stage
 
       // ---- staging, second half: the samples loaded at the top of the round go to LDS for the next iteration's forward row stage
-      if constexpr (!LUM) {
+      if constexpr (IN) {
         if (qs < NB) {
           float* pl = sm.plane[blk];
-          *reinterpret_cast<float4*>(pl + so0) = pk0 ? st0.get() : fetch_edge(sg0, t0 + qs);
-          if (has1) *reinterpret_cast<float4*>(pl + so1) = pk1 ? st1.get() : fetch_edge(sg1, t0 + qs);
+          *reinterpret_cast<float4*>(pl + so0) = st0.get();
+          if (has1) *reinterpret_cast<float4*>(pl + so1) = st1.get();
+        }
+      } else if constexpr (!LUM) {
+        if (qs < NB) {
+          float* pl = sm.plane[blk];
+          *reinterpret_cast<float4*>(pl + so0) = in0 ? st0.get() : fetch_edge(hi0 ? r_hi : r_lo, col0);
+          if (has1) *reinterpret_cast<float4*>(pl + so1) = in1 ? st1.get() : fetch_edge(r_hi, col1);
         }
       } else {
 #pragma clang fp contract(off)
@@ -551,6 +569,38 @@ __global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ i
 #if defined(TDK_EXPERIMENTS) && defined(TDK_YS_TIMING)
   if (lane == 0 && blockIdx.x == 200)
     for (int k = 0; k < 7; k++) g_ys_phase_cycles[wave][k] += ys_acc[k];
+#endif
+}
+
+// general_only: every workgroup takes the general body (TDK_WIENER_GENERAL_BODY, include/tdk_hip_wiener.h: the same bits).
+template <typename T, bool LUM>
+__global__ __launch_bounds__(256, 2) void wiener_ystream(const T* __restrict__ img, float* __restrict__ slabs, int W, int H, int C, int chan0, int vec_ok, Geom g,
+                                                         const float* __restrict__ sigmas, YParams yp, size_t plane_stride, float lum_eps, int general_only) {
+  __shared__ Smem sm;
+#if defined(TDK_EXPERIMENTS) && defined(TDK_YS_TIMING)
+  if (threadIdx.x == 0 && blockIdx.x < 2048u) g_ys_wg_times[2 * blockIdx.x] = wall_clock64();
+#endif
+  int chan = chan0;
+  const int ngroups = g.ngx * g.ngy;
+  const int plane = blockIdx.x / ngroups;
+  const Interior ir = interior_range(W, H, g.TR, !LUM && vec_ok && C == 1);
+  int gx, gy;
+  launch_order(ir, g.ngx, g.ngy, (int)blockIdx.x - plane * ngroups, gx, gy);
+  const float sigma = sigmas[chan + plane];
+  if (C == 3) chan += plane;  // interleaved input: group set p works on channel p of the same image
+  const float sig2 = sigma * sigma;
+  const T* base = img + (size_t)plane * plane_stride;
+  float* slab = slabs + (size_t)(plane * ngroups + gy * g.ngx + gx) * (size_t)(g.RSY * g.RSXP);
+  if constexpr (!LUM) {
+    if (is_interior(ir, gx, gy) && !general_only) {  // workgroup-uniform
+      ystream_body<T, false, true>(sm, base, slab, W, H, C, chan, vec_ok, g, gx, gy, sig2, yp, lum_eps);
+    } else {
+      ystream_body<T, false, false>(sm, base, slab, W, H, C, chan, vec_ok, g, gx, gy, sig2, yp, lum_eps);
+    }
+  } else {
+    ystream_body<T, true, false>(sm, base, slab, W, H, C, chan, vec_ok, g, gx, gy, sig2, yp, lum_eps);
+  }
+#if defined(TDK_EXPERIMENTS) && defined(TDK_YS_TIMING)
   if (threadIdx.x == 0 && blockIdx.x < 2048u) g_ys_wg_times[2 * blockIdx.x + 1] = wall_clock64();
 #endif
 }

@@ -43,6 +43,7 @@
 
 #include <type_traits>
 
+#include "../../include/tdk_hip_wiener.h"
 #include "tdk_color.h"
 #include "tdk_wave_fft.h"
 #include "tdk_wave_fft_pk.h"
@@ -753,7 +754,7 @@ ys::YParams make_yparams() {
 }
 
 template <typename T>
-int launch_tiles_ys(const T* in, float* slabs, int W, int H, int C, int c, const float* sigmas, const Geom& g, hipStream_t st_, int nplanes) {
+int launch_tiles_ys(const T* in, float* slabs, int W, int H, int C, int c, const float* sigmas, const Geom& g, hipStream_t st_, int nplanes, unsigned flags = 0) {
   const int vec_ok = W % 4 == 0 && (C == 1 ? tdk_aligned(in, 4 * sizeof(T)) : (C == 3 && tdk_aligned(in, 16)));
   static const ys::YParams yp = make_yparams();
   size_t lds_pad = 0;
@@ -764,8 +765,14 @@ int launch_tiles_ys(const T* in, float* slabs, int W, int H, int C, int c, const
     if (rcl != TDK_OK) return rcl;
   }
 #endif
-  TDK_LAUNCH("tdk_wiener(tiles)", (ys::wiener_ystream<T, false>), dim3((unsigned)(g.ngx * g.ngy * nplanes)), dim3(256), lds_pad, st_, in, slabs, W, H, C, c, vec_ok, g, sigmas,
-             yp, C == 1 ? (size_t)W * H : (size_t)0, 0.0f);
+  // One kernel holds both bodies of the round loop and takes the interior one for every workgroup clear of the frame's edges
+  // (ys::is_interior); TDK_WIENER_GENERAL_BODY runs it with the general body alone, under a timer name of its own.
+  if (flags & TDK_WIENER_GENERAL_BODY)
+    TDK_LAUNCH("tdk_wiener(tiles,general)", (ys::wiener_ystream<T, false>), dim3((unsigned)(g.ngx * g.ngy * nplanes)), dim3(256), lds_pad, st_, in, slabs, W, H, C, c, vec_ok, g,
+               sigmas, yp, C == 1 ? (size_t)W * H : (size_t)0, 0.0f, 1);
+  else
+    TDK_LAUNCH("tdk_wiener(tiles)", (ys::wiener_ystream<T, false>), dim3((unsigned)(g.ngx * g.ngy * nplanes)), dim3(256), lds_pad, st_, in, slabs, W, H, C, c, vec_ok, g, sigmas,
+               yp, C == 1 ? (size_t)W * H : (size_t)0, 0.0f, 0);
   return TDK_OK;
 }
 
@@ -775,7 +782,7 @@ int launch_tiles_ys_lum(const T* rgb, float* slabs, int W, int H, const float* s
   const int vec_ok = W % 4 == 0 && tdk_aligned(rgb, 16);
   static const ys::YParams yp = make_yparams();
   TDK_LAUNCH("tdk_wiener(tiles)", (ys::wiener_ystream<T, true>), dim3((unsigned)(g.ngx * g.ngy)), dim3(256), 0, st_, rgb, slabs, W, H, 3, 0, vec_ok, g, sigma, yp, (size_t)0,
-             eps);
+             eps, 1);
   return TDK_OK;
 }
 
@@ -865,7 +872,7 @@ inline unsigned stream_blocks(int64_t npix) {
 }
 
 template <typename T, int K>
-int launch(const void* in, void* out, void* workspace, int W, int H, int C, int ov, const float* sigmas, hipStream_t st_) {
+int launch(const void* in, void* out, void* workspace, int W, int H, int C, int ov, const float* sigmas, hipStream_t st_, unsigned flags = 0) {
   TDK_REQUIRE(window_table_ok<K>(), "tdk_wiener: the compiled-in window table does not match make_window()");
   const bool ysk = use_ystream(K, ov);
   const Geom g = ysk ? geometry_ys(W, H, pick_segment_rows(W, H, C == 3 ? 3 : 1)) : geometry(W, H, K, ov, pick_group_width(W, H, K, ov, C == 3 ? 3 : 1, tiles_per_cu(K, ov)));
@@ -875,7 +882,7 @@ int launch(const void* in, void* out, void* workspace, int W, int H, int C, int 
     // one tile launch over 3 x groups (group set p = channel p, read straight from the interleaved image) -> one
     // finish that writes whole RGB pixels
     const bool vec = (W % 4) == 0 && tdk_aligned(in, 16) && tdk_aligned(out, 16);
-    const int rc = ysk ? launch_tiles_ys<T>(reinterpret_cast<const T*>(in), slabs, W, H, 3, 0, sigmas, g, st_, 3)
+    const int rc = ysk ? launch_tiles_ys<T>(reinterpret_cast<const T*>(in), slabs, W, H, 3, 0, sigmas, g, st_, 3, flags)
                        : launch_tiles<T, K>(reinterpret_cast<const T*>(in), slabs, W, H, 3, 0, ov, sigmas, g, prm, st_, 3);
     if (rc != TDK_OK) return rc;
     const dim3 fgrid((unsigned)tdk_div_up(vec ? W / 4 : W, 256), (unsigned)(H < 32768 ? H : 32768));
@@ -884,7 +891,7 @@ int launch(const void* in, void* out, void* workspace, int W, int H, int C, int 
     return TDK_OK;
   }
   for (int c = 0; c < C; c++) {
-    const int rc = ysk ? launch_tiles_ys<T>(reinterpret_cast<const T*>(in), slabs, W, H, C, c, sigmas, g, st_, 1)
+    const int rc = ysk ? launch_tiles_ys<T>(reinterpret_cast<const T*>(in), slabs, W, H, C, c, sigmas, g, st_, 1, flags)
                        : launch_tiles<T, K>(reinterpret_cast<const T*>(in), slabs, W, H, C, c, ov, sigmas, g, prm, st_);
     if (rc != TDK_OK) return rc;
     TDK_LAUNCH("tdk_wiener(finish)", wiener_finish<T>, dim3((unsigned)tdk_div_up(W, 256), (unsigned)(H < 32768 ? H : 32768)), dim3(256), 0, st_, slabs,
@@ -933,7 +940,7 @@ int launch_log_luminance(const void* rgb_in, void* rgb_out, void* workspace, int
 // The Lab hand-over form of Wiener.process_log_luminance: extract log-L + (a, b) -> tiles -> wiener_finish_lab.
 template <int K>
 int launch_log_luminance_lab(const void* rgb_in, void* workspace, int W, int H, int ov, const float* sigma, float eps, int dtype, hipStream_t st_, float* lum_out,
-                             float* ab_out, const float* bounds) {
+                             float* ab_out, const float* bounds, unsigned flags = 0) {
   TDK_REQUIRE(window_table_ok<K>(), "tdk_wiener: the compiled-in window table does not match make_window()");
   const bool ysk = use_ystream(K, ov);
   const Geom g = ysk ? geometry_ys(W, H, pick_segment_rows(W, H, 1)) : geometry(W, H, K, ov, pick_group_width(W, H, K, ov, 1, tiles_per_cu(K, ov)));
@@ -946,7 +953,7 @@ int launch_log_luminance_lab(const void* rgb_in, void* workspace, int W, int H, 
 #endif
   rc = tdk_compute_log_luminance_lab(rgb_in, plane, ab_out, (int64_t)W * H, eps, bounds, dtype, reinterpret_cast<tdk_stream_t>(st_));
   if (rc != TDK_OK) return rc;
-  rc = ysk ? launch_tiles_ys<float>(plane, slabs, W, H, 1, 0, sigma, g, st_, 1) : launch_tiles<float, K>(plane, slabs, W, H, 1, 0, ov, sigma, g, prm, st_);
+  rc = ysk ? launch_tiles_ys<float>(plane, slabs, W, H, 1, 0, sigma, g, st_, 1, flags) : launch_tiles<float, K>(plane, slabs, W, H, 1, 0, ov, sigma, g, prm, st_);
   if (rc != TDK_OK) return rc;
   const dim3 fgrid((unsigned)tdk_div_up((W % 4) == 0 ? W / 4 : W, 256), (unsigned)(H < 32768 ? H : 32768));
   if ((W % 4) == 0 && tdk_aligned(ab_out, 16) && tdk_aligned(lum_out, 16))
@@ -975,8 +982,32 @@ TDK_EXPORT size_t tdk_wiener_workspace_bytes(int width, int height, int channels
   return tdk_align_up((size_t)(channels == 3 ? 3 : 1) * slabs * sizeof(float), 256);  // one slab set per channel
 }
 
+TDK_EXPORT int tdk_wiener_abi_version(void) { return TDK_WIENER_ABI_VERSION; }
+
+TDK_EXPORT int tdk_wiener_strip_interior(int width, int height, int segment_rows, int strip, int segment) {
+  if (width < 32 || height < 32 || segment_rows < YS_TR_MIN || strip < 0 || segment < 0) return -1;
+  const Geom g = geometry_ys(width, height, segment_rows);
+  if (strip >= g.ngx || segment >= g.ngy) return 0;
+  return ys::is_interior(ys::interior_range(width, height, segment_rows, width % 4 == 0), strip, segment) ? 1 : 0;
+}
+
+TDK_EXPORT int tdk_wiener_strip_order(int width, int height, int segment_rows, int workgroup) {
+  if (width < 32 || height < 32 || segment_rows < YS_TR_MIN || workgroup < 0) return -1;
+  const Geom g = geometry_ys(width, height, segment_rows);
+  if (workgroup >= g.ngx * g.ngy) return -1;
+  int gx, gy;
+  ys::launch_order(ys::interior_range(width, height, segment_rows, width % 4 == 0), g.ngx, g.ngy, workgroup, gx, gy);
+  return gy * g.ngx + gx;
+}
+
 TDK_EXPORT int tdk_wiener(const void* in, void* out, void* workspace, int width, int height, int channels, int tile_size, int overlap_factor,
                           const float* sigmas, int dtype, tdk_stream_t stream) {
+  return tdk_wiener_ex(in, out, workspace, width, height, channels, tile_size, overlap_factor, sigmas, dtype, 0u, stream);
+}
+
+TDK_EXPORT int tdk_wiener_ex(const void* in, void* out, void* workspace, int width, int height, int channels, int tile_size, int overlap_factor,
+                             const float* sigmas, int dtype, uint32_t flags, tdk_stream_t stream) {
+  TDK_REQUIRE((flags & ~TDK_WIENER_GENERAL_BODY) == 0, "tdk_wiener: unknown flags 0x%x", flags);
   TDK_REQUIRE(in && out && workspace && sigmas, "tdk_wiener: null pointer");
   TDK_REQUIRE(channels == 1 || channels == 3, "input channels must be 1 or 3, got %d", channels);
   TDK_REQUIRE(tile_size == 16 || tile_size == 32, "tile_size must be 16 or 32, got %d", tile_size);
@@ -984,8 +1015,8 @@ TDK_EXPORT int tdk_wiener(const void* in, void* out, void* workspace, int width,
   TDK_REQUIRE(width >= tile_size && height >= tile_size, "tdk_wiener: image %dx%d smaller than the tile size %d (reflect padding undefined)",
               width, height, tile_size);
   hipStream_t s = tdk_stream(stream);
-  if (tile_size == 16) TDK_DISPATCH_DTYPE(dtype, T, return (launch<T, 16>(in, out, workspace, width, height, channels, overlap_factor, sigmas, s)));
-  TDK_DISPATCH_DTYPE(dtype, T, return (launch<T, 32>(in, out, workspace, width, height, channels, overlap_factor, sigmas, s)));
+  if (tile_size == 16) TDK_DISPATCH_DTYPE(dtype, T, return (launch<T, 16>(in, out, workspace, width, height, channels, overlap_factor, sigmas, s, flags)));
+  TDK_DISPATCH_DTYPE(dtype, T, return (launch<T, 32>(in, out, workspace, width, height, channels, overlap_factor, sigmas, s, flags)));
   return TDK_OK;
 }
 
@@ -1024,6 +1055,12 @@ TDK_EXPORT int tdk_wiener_log_luminance_lum(const void* rgb_in, void* rgb_out, v
 
 TDK_EXPORT int tdk_wiener_log_luminance_lab(const void* rgb_in, void* workspace, int width, int height, int tile_size, int overlap_factor, const float* sigma,
                                             float eps, const float* bounds, int dtype, float* lum_out, float* ab_out, tdk_stream_t stream) {
+  return tdk_wiener_log_luminance_lab_ex(rgb_in, workspace, width, height, tile_size, overlap_factor, sigma, eps, bounds, dtype, lum_out, ab_out, 0u, stream);
+}
+
+TDK_EXPORT int tdk_wiener_log_luminance_lab_ex(const void* rgb_in, void* workspace, int width, int height, int tile_size, int overlap_factor, const float* sigma,
+                                               float eps, const float* bounds, int dtype, float* lum_out, float* ab_out, uint32_t flags, tdk_stream_t stream) {
+  TDK_REQUIRE((flags & ~TDK_WIENER_GENERAL_BODY) == 0, "tdk_wiener_log_luminance_lab: unknown flags 0x%x", flags);
   TDK_REQUIRE(rgb_in && workspace && sigma && lum_out && ab_out, "tdk_wiener_log_luminance_lab: null pointer");
   TDK_REQUIRE(tile_size == 16 || tile_size == 32, "tile_size must be 16 or 32, got %d", tile_size);
   TDK_REQUIRE(overlap_factor == 2 || overlap_factor == 4 || overlap_factor == 8, "overlap_factor must be 2, 4, or 8");
@@ -1031,6 +1068,6 @@ TDK_EXPORT int tdk_wiener_log_luminance_lab(const void* rgb_in, void* workspace,
   TDK_REQUIRE(eps > 0.0f, "Epsilon must be positive");
   TDK_REQUIRE(dtype == TDK_F32 || dtype == TDK_F16, "unsupported dtype tag %d", dtype);
   hipStream_t s = tdk_stream(stream);
-  if (tile_size == 16) return launch_log_luminance_lab<16>(rgb_in, workspace, width, height, overlap_factor, sigma, eps, dtype, s, lum_out, ab_out, bounds);
-  return launch_log_luminance_lab<32>(rgb_in, workspace, width, height, overlap_factor, sigma, eps, dtype, s, lum_out, ab_out, bounds);
+  if (tile_size == 16) return launch_log_luminance_lab<16>(rgb_in, workspace, width, height, overlap_factor, sigma, eps, dtype, s, lum_out, ab_out, bounds, flags);
+  return launch_log_luminance_lab<32>(rgb_in, workspace, width, height, overlap_factor, sigma, eps, dtype, s, lum_out, ab_out, bounds, flags);
 }

@@ -62,22 +62,26 @@ _verify = threading.local()
 
 @contextlib.contextmanager
 def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False, rcd_exact: bool = False, bilateral_runtime_geometry: bool = False,
-                       bilateral_general_body: bool = False):
+                       bilateral_general_body: bool = False, wiener_general_body: bool = False):
   """Inside the context (this thread only) RCD.process takes the tile kernel and / or Bilateral the four-kernel path.
   rcd_exact: a float16 result of RCD.process is the exact flavour's result rounded once (TDK_RCD_EXACT) instead of the default
   approximate arithmetic of the column strips (include/tdk_hip.h); float32 results are always exact.
   bilateral_runtime_geometry: Bilateral.process_lab runs the tile kernel that reads its grid geometry from its arguments where the
   one compiled for the default sigmas' geometry would run (TDK_BILATERAL_RUNTIME_GEOMETRY: the same bits).
   bilateral_general_body: where Bilateral.process_lab runs that constant-geometry kernel, every tile takes its general body, also
-  the tiles off the frame's edge that would take the interior body (TDK_BILATERAL_GENERAL_BODY: the same bits)."""
-  old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0), getattr(_verify, 'bil_lab', 0))
+  the tiles off the frame's edge that would take the interior body (TDK_BILATERAL_GENERAL_BODY: the same bits).
+  wiener_general_body: in Wiener.process and Wiener.process_log_luminance_lab every workgroup of the strip kernel takes its general
+  body, also those clear of every frame edge that would take the interior body (TDK_WIENER_GENERAL_BODY, include/tdk_hip_wiener.h:
+  the same bits)."""
+  old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0), getattr(_verify, 'bil_lab', 0), getattr(_verify, 'wiener', 0))
   _verify.rcd = (TDK_RCD_TILE_KERNEL if rcd_tiles else 0) | (TDK_RCD_EXACT if rcd_exact else 0)
   _verify.bil = (TDK_BILATERAL_GENERAL_PATH if bilateral_general else 0) | (TDK_BILATERAL_RUNTIME_GEOMETRY if bilateral_runtime_geometry else 0)
   _verify.bil_lab = TDK_BILATERAL_GENERAL_BODY if bilateral_general_body else 0  # the Lab entry point's own flag
+  _verify.wiener = _native.TDK_WIENER_GENERAL_BODY if wiener_general_body else 0
   try:
     yield
   finally:
-    _verify.rcd, _verify.bil, _verify.bil_lab = old
+    _verify.rcd, _verify.bil, _verify.bil_lab, _verify.wiener = old
 
 
 @contextlib.contextmanager
@@ -701,7 +705,8 @@ class Wiener(_Workspace):
     with torch.cuda.device(x.device):
       nbytes = lib.tdk_wiener_workspace_bytes(w, h, c, self._tile_size, self._overlap_factor)
       ws = self._workspace(nbytes, x.device)
-      check(lib.tdk_wiener(_ptr(x), _ptr(out), _ptr(ws), w, h, c, self._tile_size, self._overlap_factor, _ptr(sig), _dtype_tag(x), _stream()))
+      check(lib.tdk_wiener_ex(_ptr(x), _ptr(out), _ptr(ws), w, h, c, self._tile_size, self._overlap_factor, _ptr(sig), _dtype_tag(x),
+                              getattr(_verify, 'wiener', 0), _stream()))
     return out
 
   def process_log_luminance(self, image: torch.Tensor, noise_sigmas: torch.Tensor, eps: float = 1e-4, luminance_out: torch.Tensor | None = None,
@@ -758,8 +763,8 @@ class Wiener(_Workspace):
       ws = self._workspace(nbytes, x.device)
       if bounds is not None:
         _require(bounds.dtype == torch.float32 and bounds.numel() == 2 and bounds.device == x.device and bounds.is_contiguous(), 'bounds must be 2 float32 values on the image device')
-      check(lib.tdk_wiener_log_luminance_lab(_ptr(x), _ptr(ws), self._width, self._height, self._tile_size, self._overlap_factor, _ptr(sig), float(eps),
-                                             _ptr(bounds), _dtype_tag(x), _ptr(lum), _ptr(ab), _stream()))
+      check(lib.tdk_wiener_log_luminance_lab_ex(_ptr(x), _ptr(ws), self._width, self._height, self._tile_size, self._overlap_factor, _ptr(sig), float(eps),
+                                                _ptr(bounds), _dtype_tag(x), _ptr(lum), _ptr(ab), getattr(_verify, 'wiener', 0), _stream()))
     return lum, ab
 
 
