@@ -252,6 +252,16 @@ WIENER_SIGNATURES = {
   'tdk_wiener_strip_order': (c_int, [c_int, c_int, c_int, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_dehaze.h, the haze removal (weights: a host pointer to 3 floats; the others device pointers)
+DEHAZE_SIGNATURES = {
+  'tdk_dehaze_abi_version': (c_int, []),
+  'tdk_dehaze_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_dehaze_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_dehaze_ambient': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+  'tdk_dehaze': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p,
+                         c_int, c_void_p]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -270,6 +280,7 @@ HEADERS = (
   ('tdk_hip_ca.h', CA_SIGNATURES, 'tdk_ca_abi_version', 1, 'chromatic aberration ABI'),
   ('tdk_hip_rawcodec.h', RAWCODEC_SIGNATURES, 'tdk_rawcodec_abi_version', 1, 'raw codec ABI'),
   ('tdk_hip_toneeq.h', TONEEQ_SIGNATURES, 'tdk_toneeq_abi_version', 1, 'tone equalizer ABI'),
+  ('tdk_hip_dehaze.h', DEHAZE_SIGNATURES, 'tdk_dehaze_abi_version', 1, 'dehaze ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
@@ -322,6 +333,8 @@ TDK_RAWCODEC_BAD_MAGIC, TDK_RAWCODEC_BAD_SIZE, TDK_RAWCODEC_BAD_TABLES = 1, 2, 4
 # include/tdk_hip_toneeq.h: the gain table (exposures covered, nodes per octave, entries) and the largest radius
 TDK_TONEEQ_EV_MIN, TDK_TONEEQ_EV_MAX, TDK_TONEEQ_STEPS, TDK_TONEEQ_TABLE = -16, 4, 32, 641
 TDK_TONEEQ_MAX_RADIUS = 8
+# include/tdk_hip_dehaze.h: the largest radii and grid, the float32 cell planes of the workspace
+TDK_DEHAZE_MAX_DARK_RADIUS, TDK_DEHAZE_MAX_RADIUS, TDK_DEHAZE_MAX_CELLS, TDK_DEHAZE_PLANES = 4, 8, 1 << 24, 10
 TDK_WIENER_GENERAL_BODY = 1  # include/tdk_hip_wiener.h: flags of tdk_wiener_ex and tdk_wiener_log_luminance_lab_ex
 
 

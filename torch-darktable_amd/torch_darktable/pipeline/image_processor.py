@@ -30,6 +30,7 @@ from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
 from ..temporal import TemporalDenoise
+from ..dehaze import Dehaze
 from ..toneequal import ToneEqualizer
 from ..wavelet import Wavelet
 from ..white_balance import apply_white_balance
@@ -51,6 +52,11 @@ class ImageSizeMismatchError(Exception):
 
 
 class ImageProcessor:
+    # haze removal on every demosaiced frame, behind `color` and in front of the tone equalizer: the property `dehaze` (every
+    # constructor slot is pinned by the test of an earlier stage).  A class-level default, so that an object made without the
+    # constructor has the slot too; None: the reference's chain
+    _dehaze: Dehaze | None = None
+
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
                  transforms: ImageTransform | dict[str, ImageTransform] = ImageTransform.none, chromatic: ChromaticAberration | None = None, padding: int = 0, hdr: HdrMerge | None = None,
@@ -217,6 +223,21 @@ class ImageProcessor:
     @property
     def final_size(self) -> tuple[int, int]:
         return resize_longest_edge(self.image_size, self.settings.resize_width)
+
+    @property
+    def dehaze(self) -> Dehaze | None:
+        """The haze removal run on every demosaiced frame behind `color` and in front of `tone_equalizer`, so that bounds and metrics see
+        its result; None: no such stage."""
+        return self._dehaze
+
+    @dehaze.setter
+    def dehaze(self, stage: Dehaze | None) -> None:
+        if stage is not None:
+            if not isinstance(stage, Dehaze):
+                raise TypeError(f'dehaze must be a Dehaze or None, got {type(stage).__name__}')
+            if stage.image_size != tuple(self.image_size):
+                raise ValueError(f'dehaze is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
+        self._dehaze = stage
 
     @property
     def tone_equalizer(self) -> ToneEqualizer | None:
@@ -477,6 +498,8 @@ class ImageProcessor:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
         if self.color is not None:
             rgb = [self.color.process(img) for img in rgb]
+        if self._dehaze is not None:
+            rgb = [self._dehaze.process(img) for img in rgb]
         if self._tone_equalizer is not None:
             rgb = [self._tone_equalizer.process(img) for img in rgb]
         if self.exposure is not None and len(rgb) > self.exposure.max_frames:
