@@ -262,6 +262,13 @@ DEHAZE_SIGNATURES = {
                          c_int, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_filmic.h, the scene-referred tone mapping (weights: a host pointer to 3 floats; the others device pointers)
+FILMIC_SIGNATURES = {
+  'tdk_filmic_abi_version': (c_int, []),
+  'tdk_filmic_lds_bytes': (c_size_t, []),
+  'tdk_filmic': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+}
+
 # one row per public header, in the order of build.HEADERS:
 # (header, its signature table, its version function, the version this package was written against, its name in the ImportError)
 HEADERS = (
@@ -281,6 +288,7 @@ HEADERS = (
   ('tdk_hip_rawcodec.h', RAWCODEC_SIGNATURES, 'tdk_rawcodec_abi_version', 1, 'raw codec ABI'),
   ('tdk_hip_toneeq.h', TONEEQ_SIGNATURES, 'tdk_toneeq_abi_version', 1, 'tone equalizer ABI'),
   ('tdk_hip_dehaze.h', DEHAZE_SIGNATURES, 'tdk_dehaze_abi_version', 1, 'dehaze ABI'),
+  ('tdk_hip_filmic.h', FILMIC_SIGNATURES, 'tdk_filmic_abi_version', 1, 'filmic ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
@@ -335,6 +343,10 @@ TDK_TONEEQ_EV_MIN, TDK_TONEEQ_EV_MAX, TDK_TONEEQ_STEPS, TDK_TONEEQ_TABLE = -16, 
 TDK_TONEEQ_MAX_RADIUS = 8
 # include/tdk_hip_dehaze.h: the largest radii and grid, the float32 cell planes of the workspace
 TDK_DEHAZE_MAX_DARK_RADIUS, TDK_DEHAZE_MAX_RADIUS, TDK_DEHAZE_MAX_CELLS, TDK_DEHAZE_PLANES = 4, 8, 1 << 24, 10
+# include/tdk_hip_filmic.h: the curve tables (exposures covered, nodes per octave, entries), the encoding table, the norms
+TDK_FILMIC_EV_MIN, TDK_FILMIC_EV_MAX, TDK_FILMIC_STEPS, TDK_FILMIC_TABLE = -20, 12, 32, 1025
+TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE = -16, 513
+TDK_FILMIC_MAX, TDK_FILMIC_LUMA, TDK_FILMIC_POWER, TDK_FILMIC_NONE = 0, 1, 2, 3
 TDK_WIENER_GENERAL_BODY = 1  # include/tdk_hip_wiener.h: flags of tdk_wiener_ex and tdk_wiener_log_luminance_lab_ex
 
 

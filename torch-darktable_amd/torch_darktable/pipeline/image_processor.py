@@ -31,6 +31,7 @@ from ..resample import Resize
 from ..sharpen import Sharpen
 from ..temporal import TemporalDenoise
 from ..dehaze import Dehaze
+from ..filmic import Filmic
 from ..toneequal import ToneEqualizer
 from ..wavelet import Wavelet
 from ..white_balance import apply_white_balance
@@ -56,6 +57,9 @@ class ImageProcessor:
     # constructor slot is pinned by the test of an earlier stage).  A class-level default, so that an object made without the
     # constructor has the slot too; None: the reference's chain
     _dehaze: Dehaze | None = None
+    # the scene-referred display transform in place of `tonemap`: the property `filmic`, a class-level default for the same reason;
+    # None: the reference's mappers
+    _filmic: Filmic | None = None
 
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
@@ -238,6 +242,18 @@ class ImageProcessor:
             if stage.image_size != tuple(self.image_size):
                 raise ValueError(f'dehaze is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
         self._dehaze = stage
+
+    @property
+    def filmic(self) -> Filmic | None:
+        """The scene-referred tone mapping that takes the place of `tonemap` on every frame (uint8 out); bounds, metrics and their moving
+        averages are computed as without it.  None: the mapper of the settings."""
+        return self._filmic
+
+    @filmic.setter
+    def filmic(self, stage: Filmic | None) -> None:
+        if stage is not None and not isinstance(stage, Filmic):
+            raise TypeError(f'filmic must be a Filmic or None, got {type(stage).__name__}')
+        self._filmic = stage
 
     @property
     def tone_equalizer(self) -> ToneEqualizer | None:
@@ -510,7 +526,10 @@ class ImageProcessor:
         rgb = [self.process_rgb(img, self.bounds, acc) for img in rgb]
         metrics = acc.finish()
         self.metrics = lerp(self.metrics if self.metrics is not None else metrics, metrics, ema)
-        mapped = [self.tonemap(img, self.metrics) for img in rgb]
+        if self._filmic is not None:
+            mapped = [self._filmic.process(img) for img in rgb]
+        else:
+            mapped = [self.tonemap(img, self.metrics) for img in rgb]
         if self.look is not None:
             mapped = [self.look.process(img) for img in mapped]
         if resized and self.resize_workspace is not None:
