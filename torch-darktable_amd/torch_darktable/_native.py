@@ -262,6 +262,16 @@ DEHAZE_SIGNATURES = {
                          c_int, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_deconv.h, the capture sharpening (weights, luma: host pointers; the others device pointers)
+DECONV_SIGNATURES = {
+  'tdk_deconv_abi_version': (c_int, []),
+  'tdk_deconv_weights': (c_int, [c_float, c_void_p, c_void_p]),
+  'tdk_deconv_fused_iterations': (c_int, [c_int]),
+  'tdk_deconv_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_deconv_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_deconv': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_filmic.h, the scene-referred tone mapping (weights: a host pointer to 3 floats; the others device pointers)
 FILMIC_SIGNATURES = {
   'tdk_filmic_abi_version': (c_int, []),
@@ -289,6 +299,7 @@ HEADERS = (
   ('tdk_hip_toneeq.h', TONEEQ_SIGNATURES, 'tdk_toneeq_abi_version', 1, 'tone equalizer ABI'),
   ('tdk_hip_dehaze.h', DEHAZE_SIGNATURES, 'tdk_dehaze_abi_version', 1, 'dehaze ABI'),
   ('tdk_hip_filmic.h', FILMIC_SIGNATURES, 'tdk_filmic_abi_version', 1, 'filmic ABI'),
+  ('tdk_hip_deconv.h', DECONV_SIGNATURES, 'tdk_deconv_abi_version', 1, 'deconvolution ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
@@ -343,6 +354,9 @@ TDK_TONEEQ_EV_MIN, TDK_TONEEQ_EV_MAX, TDK_TONEEQ_STEPS, TDK_TONEEQ_TABLE = -16, 
 TDK_TONEEQ_MAX_RADIUS = 8
 # include/tdk_hip_dehaze.h: the largest radii and grid, the float32 cell planes of the workspace
 TDK_DEHAZE_MAX_DARK_RADIUS, TDK_DEHAZE_MAX_RADIUS, TDK_DEHAZE_MAX_CELLS, TDK_DEHAZE_PLANES = 4, 8, 1 << 24, 10
+# include/tdk_hip_deconv.h: the flag of tdk_deconv, the bits of its fused count, the limits, the tile of a workgroup
+TDK_DECONV_MASK, TDK_DECONV_FUSE_SHIFT, TDK_DECONV_FUSE_MASK = 1, 8, 0xF00
+TDK_DECONV_MAX_RADIUS, TDK_DECONV_MAX_ITERATIONS, TDK_DECONV_MAX_FUSED, TDK_DECONV_TILE = 6, 50, 4, 32
 # include/tdk_hip_filmic.h: the curve tables (exposures covered, nodes per octave, entries), the encoding table, the norms
 TDK_FILMIC_EV_MIN, TDK_FILMIC_EV_MAX, TDK_FILMIC_STEPS, TDK_FILMIC_TABLE = -20, 12, 32, 1025
 TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE = -16, 513

@@ -30,6 +30,7 @@ from ..rawprepare import RawPrepare
 from ..resample import Resize
 from ..sharpen import Sharpen
 from ..temporal import TemporalDenoise
+from ..deconvolve import Deconvolve
 from ..dehaze import Dehaze
 from ..filmic import Filmic
 from ..toneequal import ToneEqualizer
@@ -60,6 +61,9 @@ class ImageProcessor:
     # the scene-referred display transform in place of `tonemap`: the property `filmic`, a class-level default for the same reason;
     # None: the reference's mappers
     _filmic: Filmic | None = None
+    # capture sharpening on every demosaiced frame, behind `chroma_denoise` and in front of `color`: the property `capture_sharpen`,
+    # a class-level default for the same reason; None: no such stage
+    _capture_sharpen: Deconvolve | None = None
 
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
@@ -242,6 +246,21 @@ class ImageProcessor:
             if stage.image_size != tuple(self.image_size):
                 raise ValueError(f'dehaze is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
         self._dehaze = stage
+
+    @property
+    def capture_sharpen(self) -> Deconvolve | None:
+        """The deconvolution run on every demosaiced frame behind `chroma_denoise` and in front of `color`: on linear camera RGB, after
+        the noise has been dealt with, so that every later stage sees its detail; None: no such stage."""
+        return self._capture_sharpen
+
+    @capture_sharpen.setter
+    def capture_sharpen(self, stage: Deconvolve | None) -> None:
+        if stage is not None:
+            if not isinstance(stage, Deconvolve):
+                raise TypeError(f'capture_sharpen must be a Deconvolve or None, got {type(stage).__name__}')
+            if stage.image_size != tuple(self.image_size):
+                raise ValueError(f'capture_sharpen is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
+        self._capture_sharpen = stage
 
     @property
     def filmic(self) -> Filmic | None:
@@ -512,6 +531,8 @@ class ImageProcessor:
             rgb = [m.unstabilize(self.chroma_denoise.process(m.stabilize(img, gains=wb)), gains=wb, out_dtype=img.dtype) for img in rgb]
         elif self.chroma_denoise is not None:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
+        if self._capture_sharpen is not None:
+            rgb = [self._capture_sharpen.process(img) for img in rgb]
         if self.color is not None:
             rgb = [self.color.process(img) for img in rgb]
         if self._dehaze is not None:
