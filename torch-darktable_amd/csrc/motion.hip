@@ -6,7 +6,8 @@
 //
 // Pyramid, mo_pyramid<TS>: a workgroup of 256 lanes owns the 32 x 16 level-0 values of one tile of the temporal filter (64 x 32 sites).
 // A lane turns two CFA cells into grey values, the tile goes to LDS, and level k + 1 is reduced from level k there: the tile's origin
-// is a multiple of 8 values, so the 2 x 2 blocks of every level (and the clamp at the plane's last row and column) stay inside it.
+// is a multiple of 8 values, so the 2 x 2 blocks of every level (and the clamp at the plane's last row and column) stay inside it.  The
+// body stands in tdk_motion_pyramid.h, which hdralign.hip instantiates a second time with the scale of a bracket's frame.
 // Match, mo_match: one wave per tile.  Per level the block (16 x 32 bytes) and the search window ((16 + 2R) x (32 + 2R) bytes, fetched
 // with clamped coordinates, so the LDS copy answers ref[clamp(p + d)] for every candidate) are staged as dwords; a lane owns a
 // candidate and walks the block four samples per v_sad_u8, the window dword shifted into place from two neighbours; the winner is the
@@ -17,107 +18,22 @@
 // lane's group goes as 16-byte vectors or per element is decided by the shifted address, as tp_filter decides by the plain one.  The
 // entry point shares the checks of tdk_temporal_denoise (tt_check); the pyramid reads its sites with mt_fetch of tdk_mosaic_tile.h.
 #include "../../include/tdk_hip_motion.h"
+#include "tdk_motion_pyramid.h"
 #include "tdk_temporal_tile.h"
 
 namespace {
 
-constexpr int MO_BW = 32, MO_BH = 16;                 // the block of a tile at every level; the tile's level-0 values
-constexpr int MO_THREADS = 256;                       // of the pyramid launch
 constexpr int MO_WAVE = 64;                           // of the match launch
 constexpr int MO_WIN_DWORDS = (MO_BW + 2 * TDK_MOTION_MAX_SEARCH) / 4 + 1;   // dwords of a staged window row: one more than the
                                                                              // widest window, for the shifted read of the last group
 constexpr int MO_WIN_ROWS = MO_BH + 2 * TDK_MOTION_MAX_SEARCH;
-static_assert(2 * MO_BW == TDK_MOTION_TILE_W && 2 * MO_BH == TDK_MOTION_TILE_H, "a tile is its level-0 block");
 static_assert(TDK_MOTION_TILE_W == TDK_TEMPORAL_TILE_W && TDK_MOTION_TILE_H == TDK_TEMPORAL_TILE_H, "the tiles of the temporal filter");
 static_assert(2 * ((TDK_MOTION_MAX_SEARCH + 1) * (1 << (TDK_MOTION_MAX_LEVELS - 1)) - 1) == TDK_MOTION_MAX_DISPLACEMENT, "the largest displacement");
 
-struct MoGeometry {
-  int w[TDK_MOTION_MAX_LEVELS], h[TDK_MOTION_MAX_LEVELS];
-  size_t at[TDK_MOTION_MAX_LEVELS];   // byte offset of a level in its slot
-  size_t slot;                        // bytes of a slot
-};
-
-MoGeometry mo_geometry(int width, int height, int levels) {
-  MoGeometry g{};
-  int w = width / 2, h = height / 2;
-  for (int k = 0; k < levels; k++) {
-    g.w[k] = w, g.h[k] = h, g.at[k] = g.slot;
-    g.slot += tdk_align_up((size_t)w * (size_t)h, 16);
-    w = (w + 1) / 2, h = (h + 1) / 2;
-  }
-  return g;
-}
-
-bool mo_levels_ok(int levels) { return levels >= 1 && levels <= TDK_MOTION_MAX_LEVELS; }
-
-// ================================================================ pyramid
-struct MoPyramidArgs {
-  const void* src;
-  unsigned char* pyramid;
-  const uint32_t* index;
-  int which, levels, w, h;   // w, h: sites
-  float scale;
-  MoGeometry g;
-};
-
-__device__ __forceinline__ uint32_t mo_grey(float x00, float x01, float x10, float x11, float scale) {
-  const float q = (x00 + x01) + (x10 + x11);
-  const float u = fminf(fmaxf(q * scale, 0.0f), 1.0f);
-  return (uint32_t)(__fsqrt_rn(u) * 255.0f + 0.5f);
-}
-
+// ================================================================ pyramid (the tile body of tdk_motion_pyramid.h)
 template <typename TS> __global__ __launch_bounds__(MO_THREADS) void mo_pyramid(MoPyramidArgs a) {
-  // the tile at every level, one behind the other: 16 x 32, 8 x 16, 4 x 8, 2 x 4 values
-  __shared__ unsigned char lds[MO_BH * MO_BW * 2];
-  const int tid = threadIdx.x;
-  const uint32_t slot = a.index ? ((*a.index + (uint32_t)a.which) & 1u) : (uint32_t)a.which;
-  unsigned char* __restrict__ dst = a.pyramid + (size_t)slot * a.g.slot;
-  const TS* __restrict__ src = reinterpret_cast<const TS*>(a.src);
-
-  // ---- level 0: two cells of tile row r
-  {
-    const int r = tid / (MO_BW / 2), cp = tid % (MO_BW / 2);
-    const int I = (int)blockIdx.y * MO_BH + r, J = (int)blockIdx.x * MO_BW + 2 * cp;
-    const int cells = I < a.g.h[0] ? min(max(a.g.w[0] - J, 0), 2) : 0;
-    uint32_t g[2] = {0u, 0u};
-    if (cells > 0) {
-      float top[4], bottom[4];
-      const size_t at = (size_t)(2 * I) * (size_t)a.w + (size_t)(2 * J);
-      mt_fetch<TS, 4>(src, (int64_t)at, 0, 2 * cells, top);
-      mt_fetch<TS, 4>(src, (int64_t)(at + (size_t)a.w), 0, 2 * cells, bottom);
-      g[0] = mo_grey(top[0], top[1], bottom[0], bottom[1], a.scale);
-      if (cells > 1) g[1] = mo_grey(top[2], top[3], bottom[2], bottom[3], a.scale);
-#pragma unroll
-      for (int m = 0; m < 2; m++)
-        if (m < cells) dst[a.g.at[0] + (size_t)I * (size_t)a.g.w[0] + (size_t)(J + m)] = (unsigned char)g[m];
-    }
-    lds[r * MO_BW + 2 * cp] = (unsigned char)g[0];
-    lds[r * MO_BW + 2 * cp + 1] = (unsigned char)g[1];
-  }
-
-  // ---- level k + 1 from level k of the tile
-  int from = 0;   // where level k starts in lds
-  for (int k = 0; k + 1 < a.levels; k++) {
-    __syncthreads();
-    const int pw = MO_BW >> k, ph = MO_BH >> k;      // the tile at level k
-    const int tw = pw >> 1, th = ph >> 1;            // ... and at level k + 1
-    const int to = from + pw * ph;
-    if (tid < tw * th) {
-      const int r = tid / tw, c = tid % tw;
-      const int R = (((int)blockIdx.y * MO_BH) >> (k + 1)) + r, Cc = (((int)blockIdx.x * MO_BW) >> (k + 1)) + c;
-      uint32_t v = 0u;
-      if (R < a.g.h[k + 1] && Cc < a.g.w[k + 1]) {
-        // the clamp to the last row and column of level k, in the tile's coordinates: its origin at level k is twice that at level k + 1
-        const int r1 = 2 * r + ((2 * R + 1 < a.g.h[k]) ? 1 : 0), c1 = 2 * c + ((2 * Cc + 1 < a.g.w[k]) ? 1 : 0);
-        const uint32_t s = (uint32_t)lds[from + 2 * r * pw + 2 * c] + (uint32_t)lds[from + 2 * r * pw + c1] + (uint32_t)lds[from + r1 * pw + 2 * c] +
-                           (uint32_t)lds[from + r1 * pw + c1];
-        v = (s + 2u) >> 2;
-        dst[a.g.at[k + 1] + (size_t)R * (size_t)a.g.w[k + 1] + (size_t)Cc] = (unsigned char)v;
-      }
-      lds[to + r * tw + c] = (unsigned char)v;
-    }
-    from = to;
-  }
+  __shared__ unsigned char lds[MO_PYRAMID_LDS];
+  mo_pyramid_tile<TS>(lds, a, MoScaleGiven{});
 }
 
 // ================================================================ match
@@ -281,29 +197,12 @@ template <typename TS> int mo_launch_pyramid(const MoPyramidArgs& a, hipStream_t
 
 TDK_EXPORT int tdk_motion_abi_version(void) { return TDK_MOTION_ABI_VERSION; }
 
-TDK_EXPORT size_t tdk_motion_pyramid_bytes(int width, int height, int levels) {
-  if (!mt_size_ok(width, height) || !mo_levels_ok(levels)) return 0;
-  return 2 * mo_geometry(width, height, levels).slot;
-}
+TDK_EXPORT size_t tdk_motion_pyramid_bytes(int width, int height, int levels) { return mo_pyramid_bytes(width, height, levels); }
 
 TDK_EXPORT int tdk_motion_pyramid(const void* src, int src_dtype, int width, int height, float scale, int levels, void* pyramid, const uint32_t* index, int which,
                                   tdk_stream_t stream) {
-  static const char* const who = "tdk_motion_pyramid";
-  TDK_REQUIRE(src && pyramid, "%s: null pointer (src or pyramid)", who);
-  TDK_REQUIRE(mt_dtype_ok(src_dtype), "%s: unsupported dtype tag %d", who, src_dtype);
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= MT_MAX_SIZE && height <= MT_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, MT_MAX_SIZE);
-  TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
-  TDK_REQUIRE(isfinite(scale) && scale > 0.0f, "%s: scale must be finite and > 0", who);
-  TDK_REQUIRE(mo_levels_ok(levels), "%s: levels must be 1..%d, got %d", who, TDK_MOTION_MAX_LEVELS, levels);
-  TDK_REQUIRE(which == 0 || which == 1, "%s: which must be 0 or 1, got %d", who, which);
-  TDK_REQUIRE(tdk_aligned(pyramid, 16), "%s: pyramid must be aligned to 16 bytes", who);
-  TDK_REQUIRE(!index || tdk_aligned(index, 4), "%s: index must be aligned to 4 bytes", who);
-  const size_t src_bytes = (size_t)width * (size_t)height * tdk_dtype_bytes(src_dtype);
-  TDK_REQUIRE(tdk_disjoint(src, src_bytes, pyramid, tdk_motion_pyramid_bytes(width, height, levels)), "%s: src and pyramid overlap", who);
-
   MoPyramidArgs a{};
-  a.src = src, a.pyramid = reinterpret_cast<unsigned char*>(pyramid), a.index = index, a.which = which, a.levels = levels;
-  a.w = width, a.h = height, a.scale = scale, a.g = mo_geometry(width, height, levels);
+  if (const int rc = mo_check_pyramid("tdk_motion_pyramid", src, src_dtype, width, height, scale, levels, pyramid, index, which, a)) return rc;
   hipStream_t st = tdk_stream(stream);
   return src_dtype == TDK_F32 ? mo_launch_pyramid<float>(a, st) : mo_launch_pyramid<__half>(a, st);
 }

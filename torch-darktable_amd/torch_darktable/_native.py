@@ -215,6 +215,15 @@ HDR_SIGNATURES = {
                             c_float, c_float, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_hdralign.h, the aligned bracket merge (frames: a host array of device pointers; the others device pointers)
+HDRALIGN_SIGNATURES = {
+  'tdk_hdralign_abi_version': (c_int, []),
+  'tdk_hdralign_lds_bytes': (c_size_t, [c_int]),
+  'tdk_hdralign_pyramid': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+  'tdk_hdralign_merge': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_uint32, c_void_p, c_int, c_void_p, c_int, c_float, c_float,
+                                 c_float, c_float, c_float, c_void_p, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_ca.h, the chromatic aberration (frames: a host array of device pointers; the others device pointers)
 CA_SIGNATURES = {
   'tdk_ca_abi_version': (c_int, []),
@@ -294,6 +303,7 @@ HEADERS = (
   ('tdk_hip_temporal.h', TEMPORAL_SIGNATURES, 'tdk_temporal_abi_version', 1, 'temporal ABI'),
   ('tdk_hip_motion.h', MOTION_SIGNATURES, 'tdk_motion_abi_version', 1, 'motion ABI'),
   ('tdk_hip_hdr.h', HDR_SIGNATURES, 'tdk_hdr_abi_version', 1, 'hdr ABI'),
+  ('tdk_hip_hdralign.h', HDRALIGN_SIGNATURES, 'tdk_hdralign_abi_version', 1, 'hdr alignment ABI'),
   ('tdk_hip_ca.h', CA_SIGNATURES, 'tdk_ca_abi_version', 1, 'chromatic aberration ABI'),
   ('tdk_hip_rawcodec.h', RAWCODEC_SIGNATURES, 'tdk_rawcodec_abi_version', 1, 'raw codec ABI'),
   ('tdk_hip_toneeq.h', TONEEQ_SIGNATURES, 'tdk_toneeq_abi_version', 1, 'tone equalizer ABI'),

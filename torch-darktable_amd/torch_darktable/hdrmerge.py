@@ -147,12 +147,8 @@ class HdrMerge:
             buf.copy_(torch.tensor(exposures, dtype=torch.float32))
         return buf
 
-    def process(self, frames, exposures, ref: int | None = None, out_dtype: torch.dtype | None = None, return_mask: bool = False):
-        """A bracket -> the merged mosaic, a fresh tensor; with return_mask also the (H, W) uint8 mask: the anchor frame in bits 0..2, 8
-        where every frame is clipped, the number of frames with weight in bits 4..7.  frames: a list of (H, W) tensors or one (F, H, W)
-        tensor, all float32 or all float16, each contiguous.  exposures: F floats (finite and > 0; uploaded once per distinct tuple and
-        stream) or a device tensor of F floats, read by the kernel and not checked.  ref: the anchor frame of the sites it does not clip;
-        None: the longest exposure."""
+    def _arguments(self, frames, exposures, ref, out_dtype):
+        """The checks of `process`: (frames as a list, the exposures as the host holds them, out_dtype, the model tensor)."""
         frames = self._frames(frames)
         count = len(frames)
         first = frames[0]
@@ -169,6 +165,16 @@ class HdrMerge:
             _require(frame.device == first.device, 'The frames must be on one device')
         model = self._noise_model.model
         _require(model.device == first.device, 'The model must be on the device of the input')
+        return frames, exposures, out_dtype, model
+
+    def process(self, frames, exposures, ref: int | None = None, out_dtype: torch.dtype | None = None, return_mask: bool = False):
+        """A bracket -> the merged mosaic, a fresh tensor; with return_mask also the (H, W) uint8 mask: the anchor frame in bits 0..2, 8
+        where every frame is clipped, the number of frames with weight in bits 4..7.  frames: a list of (H, W) tensors or one (F, H, W)
+        tensor, all float32 or all float16, each contiguous.  exposures: F floats (finite and > 0; uploaded once per distinct tuple and
+        stream) or a device tensor of F floats, read by the kernel and not checked.  ref: the anchor frame of the sites it does not clip;
+        None: the longest exposure."""
+        frames, exposures, out_dtype, model = self._arguments(frames, exposures, ref, out_dtype)
+        count, first = len(frames), frames[0]
         shape = (self.height, self.width)
         with torch.cuda.device(first.device):
             exp = self._exposure_tensor(exposures, first.device)
