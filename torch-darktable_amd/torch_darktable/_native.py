@@ -281,6 +281,13 @@ DECONV_SIGNATURES = {
   'tdk_deconv': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_lmmse.h, the demosaic for noisy frames (device pointers)
+LMMSE_SIGNATURES = {
+  'tdk_lmmse_abi_version': (c_int, []),
+  'tdk_lmmse_lds_bytes': (c_size_t, [c_int, c_int, c_int]),
+  'tdk_lmmse': (c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_int, c_int, c_int, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_filmic.h, the scene-referred tone mapping (weights: a host pointer to 3 floats; the others device pointers)
 FILMIC_SIGNATURES = {
   'tdk_filmic_abi_version': (c_int, []),
@@ -310,6 +317,7 @@ HEADERS = (
   ('tdk_hip_dehaze.h', DEHAZE_SIGNATURES, 'tdk_dehaze_abi_version', 1, 'dehaze ABI'),
   ('tdk_hip_filmic.h', FILMIC_SIGNATURES, 'tdk_filmic_abi_version', 1, 'filmic ABI'),
   ('tdk_hip_deconv.h', DECONV_SIGNATURES, 'tdk_deconv_abi_version', 1, 'deconvolution ABI'),
+  ('tdk_hip_lmmse.h', LMMSE_SIGNATURES, 'tdk_lmmse_abi_version', 1, 'LMMSE demosaic ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
@@ -367,6 +375,10 @@ TDK_DEHAZE_MAX_DARK_RADIUS, TDK_DEHAZE_MAX_RADIUS, TDK_DEHAZE_MAX_CELLS, TDK_DEH
 # include/tdk_hip_deconv.h: the flag of tdk_deconv, the bits of its fused count, the limits, the tile of a workgroup
 TDK_DECONV_MASK, TDK_DECONV_FUSE_SHIFT, TDK_DECONV_FUSE_MASK = 1, 8, 0xF00
 TDK_DECONV_MAX_RADIUS, TDK_DECONV_MAX_ITERATIONS, TDK_DECONV_MAX_FUSED, TDK_DECONV_TILE = 6, 50, 4, 32
+# include/tdk_hip_lmmse.h: the flag of tdk_lmmse, the output tile of a workgroup, what a stored site depends on, the sizes taken
+TDK_LMMSE_LINEAR = 1
+TDK_LMMSE_TILE_W, TDK_LMMSE_TILE_H, TDK_LMMSE_APRON = 32, 32, 11
+TDK_LMMSE_MIN_SIZE, TDK_LMMSE_MAX_SIZE = 2, 65535
 # include/tdk_hip_filmic.h: the curve tables (exposures covered, nodes per octave, entries), the encoding table, the norms
 TDK_FILMIC_EV_MIN, TDK_FILMIC_EV_MAX, TDK_FILMIC_STEPS, TDK_FILMIC_TABLE = -20, 12, 32, 1025
 TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE = -16, 513

@@ -23,6 +23,7 @@ from ..denoise import Wiener
 from ..framestats import FrameStats
 from ..hdrmerge import HdrMerge
 from ..highlights import Highlights
+from ..lmmse import LMMSE
 from ..local_contrast import Bilateral
 from ..noiseprofile import NoiseModel
 from ..rawcodec import RawCodec, RawCodecResult
@@ -64,6 +65,9 @@ class ImageProcessor:
     # capture sharpening on every demosaiced frame, behind `chroma_denoise` and in front of `color`: the property `capture_sharpen`,
     # a class-level default for the same reason; None: no such stage
     _capture_sharpen: Deconvolve | None = None
+    # the demosaic for noisy frames in place of the method `settings.debayer` names: the property `demosaic` (the Debayer enum is
+    # pinned to the reference), a class-level default for the same reason; None: the reference's three methods
+    _lmmse: LMMSE | None = None
 
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
@@ -248,6 +252,24 @@ class ImageProcessor:
         self._dehaze = stage
 
     @property
+    def demosaic(self) -> LMMSE | None:
+        """The demosaic that takes the place of the method `settings.debayer` names, still followed by PostProcess when
+        `settings.postprocess` is set; load_image then takes the unfused path (decode, white balance, demosaic), and with binary16
+        storage the stage writes binary16 itself.  None: bilinear, PPG or RCD, as `settings.debayer` says."""
+        return self._lmmse
+
+    @demosaic.setter
+    def demosaic(self, stage: LMMSE | None) -> None:
+        if stage is not None:
+            if not isinstance(stage, LMMSE):
+                raise TypeError(f'demosaic must be an LMMSE or None, got {type(stage).__name__}')
+            if stage.image_size != tuple(self.image_size):
+                raise ValueError(f'demosaic is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
+            if stage.bayer_pattern != self.bayer_pattern:
+                raise ValueError(f'demosaic is for {stage.bayer_pattern.name}, the processor for {self.bayer_pattern.name}')
+        self._lmmse = stage
+
+    @property
     def capture_sharpen(self) -> Deconvolve | None:
         """The deconvolution run on every demosaiced frame behind `chroma_denoise` and in front of `color`: on linear camera RGB, after
         the noise has been dealt with, so that every later stage sees its detail; None: no such stage."""
@@ -358,7 +380,7 @@ class ImageProcessor:
             payload = bytes[: bytes.numel() - self.padding] if self.padding > 0 else bytes
             mosaic = self.raw_correction.process_packed(payload, self.packed_format, white_balance=self.white_balance)
             return self._demosaic(mosaic).to(self.storage_dtype)   # the white balance is in the mosaic already
-        if self.settings.debayer == Debayer.rcd:
+        if self.settings.debayer == Debayer.rcd and self._lmmse is None:
             # decode -> white balance -> RCD as one kernel (same result as load_bytes + debayer, two fp32 planes less)
             if bytes.numel() != self.expected_bytes:
                 raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
@@ -406,7 +428,9 @@ class ImageProcessor:
     def _demosaic(self, bayer_image: torch.Tensor) -> torch.Tensor:
         mosaic = bayer_image.unsqueeze(-1)
         method = self.settings.debayer
-        if method == Debayer.bilinear:
+        if self._lmmse is not None:
+            rgb = self._lmmse.process(mosaic, out_dtype=self.storage_dtype)
+        elif method == Debayer.bilinear:
             rgb = _debayer.bilinear5x5_demosaic(mosaic, self.bayer_pattern)
         elif method == Debayer.rcd:
             rgb = self.rcd_workspace.process(mosaic)
