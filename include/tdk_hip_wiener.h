@@ -11,6 +11,25 @@
  * image rows starting at y = 8 (segment_rows segment - 3).  A workgroup none of whose samples lies outside the frame is INTERIOR
  * and runs a second instantiation of the kernel's round loop that carries no bounds test, no reflection and no tile-exists
  * predicate.  The two bodies differ in integer addressing and control flow only: the results are the same bits.
+ *
+ * Samples outside the usual range (every tile kernel, every tile_size and overlap_factor; tests/test_gpu_denoise_domain.py):
+ *   - Footprint.  Two horizontally adjacent tiles -- tile columns 2 m and 2 m + 1, counted from the first tile, whose origin is
+ *     x = -(overlap_factor - 1) s with s = tile_size / overlap_factor -- are the real and the imaginary part of ONE complex
+ *     transform.  A sample therefore reaches, beyond the tiles that read it (directly or mirrored at a frame edge), the partner
+ *     of each of those tiles: its rounding error is relative to the larger of the two tiles' samples, and a NaN or an infinity in
+ *     one tile makes both tiles NaN.  The pixels a sample can change are the union of those tiles and partners, cut to the frame:
+ *     up to s columns more on either side than the tile union of the reference, the same rows.  Outside that box the result
+ *     has the bits it has without the sample (no atomics, a fixed order of additions); a NaN or +-inf sample makes exactly
+ *     that box non-finite.
+ *   - Gain.  max(1 - sigma^2 / p, 0), p = |X|^2 + 1e-15, is evaluated as max(GS - (4 sigma^2 GS) * rcp(p4), 0) with the
+ *     hardware reciprocal.  Where |X|^2 overflows float32 (|X| above 1.8e19: a sample of 1e30), rcp(inf) = 0 and the gain is the
+ *     pass-through gain exactly, the value the unrounded expression has; the reference's IEEE division gives inf / inf = NaN
+ *     there.  Such a tile returns its samples, within float32 rounding relative to the largest of them.
+ *   - Mean.  A tile's mean is a float32 sum of its tile_size^2 samples, a mirrored sample counting once per read.  The result is
+ *     finite as long as that sum is: one sample of 3e38 read once is, read twice (within tile_size of a frame edge) it is not,
+ *     and the tiles whose sum overflows, with their partners, are NaN.
+ *   - The finish kernels multiply by rcp(mask + 1e-15), mask being the analytic sum of the window products over the tiles that
+ *     cover a pixel (a positive constant per column and row phase, about 1 / s^2): a factor within 1 ulp, never 0 or inf.
  */
 #ifndef TDK_HIP_WIENER_H
 #define TDK_HIP_WIENER_H
