@@ -288,6 +288,15 @@ LMMSE_SIGNATURES = {
   'tdk_lmmse': (c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_int, c_int, c_int, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_defringe.h, the purple-fringe removal (weights: a host pointer to radius + 1 floats; the others device pointers)
+DEFRINGE_SIGNATURES = {
+  'tdk_defringe_abi_version': (c_int, []),
+  'tdk_defringe_weights': (c_int, [c_float, c_void_p, c_void_p]),
+  'tdk_defringe_workspace_bytes': (c_size_t, [c_int, c_int]),
+  'tdk_defringe_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_defringe': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_filmic.h, the scene-referred tone mapping (weights: a host pointer to 3 floats; the others device pointers)
 FILMIC_SIGNATURES = {
   'tdk_filmic_abi_version': (c_int, []),
@@ -318,6 +327,7 @@ HEADERS = (
   ('tdk_hip_filmic.h', FILMIC_SIGNATURES, 'tdk_filmic_abi_version', 1, 'filmic ABI'),
   ('tdk_hip_deconv.h', DECONV_SIGNATURES, 'tdk_deconv_abi_version', 1, 'deconvolution ABI'),
   ('tdk_hip_lmmse.h', LMMSE_SIGNATURES, 'tdk_lmmse_abi_version', 1, 'LMMSE demosaic ABI'),
+  ('tdk_hip_defringe.h', DEFRINGE_SIGNATURES, 'tdk_defringe_abi_version', 1, 'defringe ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
@@ -379,6 +389,11 @@ TDK_DECONV_MAX_RADIUS, TDK_DECONV_MAX_ITERATIONS, TDK_DECONV_MAX_FUSED, TDK_DECO
 TDK_LMMSE_LINEAR = 1
 TDK_LMMSE_TILE_W, TDK_LMMSE_TILE_H, TDK_LMMSE_APRON = 32, 32, 11
 TDK_LMMSE_MIN_SIZE, TDK_LMMSE_MAX_SIZE = 2, 65535
+# include/tdk_hip_defringe.h: the flags of tdk_defringe, the bits of its workgroup cap, the limits, the tile of a workgroup, the statistic's scale and cap
+TDK_DEFRINGE_GLOBAL, TDK_DEFRINGE_LINEAR, TDK_DEFRINGE_STATIC = 0, 1, 2
+TDK_DEFRINGE_GROUPS_SHIFT, TDK_DEFRINGE_GROUPS_MASK = 8, 0x7FF00
+TDK_DEFRINGE_MAX_RADIUS, TDK_DEFRINGE_MAX_SAMPLE_RADIUS, TDK_DEFRINGE_MAX_GROUPS, TDK_DEFRINGE_TILE = 12, 8, 1024, 32
+TDK_DEFRINGE_STAT_SCALE, TDK_DEFRINGE_STAT_CAP = 1048576, 1024
 # include/tdk_hip_filmic.h: the curve tables (exposures covered, nodes per octave, entries), the encoding table, the norms
 TDK_FILMIC_EV_MIN, TDK_FILMIC_EV_MAX, TDK_FILMIC_STEPS, TDK_FILMIC_TABLE = -20, 12, 32, 1025
 TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE = -16, 513

@@ -32,6 +32,7 @@ from ..resample import Resize
 from ..sharpen import Sharpen
 from ..temporal import TemporalDenoise
 from ..deconvolve import Deconvolve
+from ..defringe import Defringe
 from ..dehaze import Dehaze
 from ..filmic import Filmic
 from ..toneequal import ToneEqualizer
@@ -65,6 +66,9 @@ class ImageProcessor:
     # capture sharpening on every demosaiced frame, behind `chroma_denoise` and in front of `color`: the property `capture_sharpen`,
     # a class-level default for the same reason; None: no such stage
     _capture_sharpen: Deconvolve | None = None
+    # purple-fringe removal on every demosaiced frame, behind `chroma_denoise` and in front of `capture_sharpen`: the property
+    # `defringe`, a class-level default for the same reason; None: no such stage
+    _defringe: Defringe | None = None
     # the demosaic for noisy frames in place of the method `settings.debayer` names: the property `demosaic` (the Debayer enum is
     # pinned to the reference), a class-level default for the same reason; None: the reference's three methods
     _lmmse: LMMSE | None = None
@@ -268,6 +272,21 @@ class ImageProcessor:
             if stage.bayer_pattern != self.bayer_pattern:
                 raise ValueError(f'demosaic is for {stage.bayer_pattern.name}, the processor for {self.bayer_pattern.name}')
         self._lmmse = stage
+
+    @property
+    def defringe(self) -> Defringe | None:
+        """The purple-fringe removal run on every demosaiced frame behind `chroma_denoise` and in front of `capture_sharpen`: noise
+        does not set its threshold, and the deconvolution does not sharpen the halo; None: no such stage."""
+        return self._defringe
+
+    @defringe.setter
+    def defringe(self, stage: Defringe | None) -> None:
+        if stage is not None:
+            if not isinstance(stage, Defringe):
+                raise TypeError(f'defringe must be a Defringe or None, got {type(stage).__name__}')
+            if stage.image_size != tuple(self.image_size):
+                raise ValueError(f'defringe is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
+        self._defringe = stage
 
     @property
     def capture_sharpen(self) -> Deconvolve | None:
@@ -555,6 +574,8 @@ class ImageProcessor:
             rgb = [m.unstabilize(self.chroma_denoise.process(m.stabilize(img, gains=wb)), gains=wb, out_dtype=img.dtype) for img in rgb]
         elif self.chroma_denoise is not None:
             rgb = [self.chroma_denoise.process(img) for img in rgb]
+        if self._defringe is not None:
+            rgb = [self._defringe.process(img) for img in rgb]
         if self._capture_sharpen is not None:
             rgb = [self._capture_sharpen.process(img) for img in rgb]
         if self.color is not None:
