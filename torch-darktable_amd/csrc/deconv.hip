@@ -37,7 +37,6 @@ namespace {
 constexpr int DC_THREADS = 256;
 constexpr int DC_T = TDK_DECONV_TILE, DC_PIX = 4, DC_GROUPS = DC_T / DC_PIX;   // 8 threads per tile row, 32 rows
 constexpr int DC_MAX_R = TDK_DECONV_MAX_RADIUS;
-constexpr int DC_MAX_SIZE = 65535;
 constexpr float DC_TINY = 0x1p-20f;
 constexpr float DC_MAX_GAIN = 16.0f;
 constexpr size_t DC_WS_ALIGN = 16;
@@ -70,21 +69,13 @@ enum : int {
   DC_VEC_IN = 16, DC_VEC_OUT = 32, DC_VEC_U = 64, DC_VEC_M = 128,   // whole vectors of four elements for src, dst, the planes of u, mask_out
 };
 
-__device__ __forceinline__ float dc_pos(float v) { return v > 0.0f ? v : 0.0f; }
-
-// e-th position of a region of `cols` columns in row order; inv = 1 / cols.  The quotient is never near an integer.
-__device__ __forceinline__ void dc_split(int e, int cols, float inv, int& r, int& c) {
-  r = (int)(((float)e + 0.5f) * inv);
-  c = e - r * cols;
-}
-
 // d = the horizontal blur of s on rows [r0, r1), columns [c0, c1), each centred on the column of its clamped pixel
 __device__ __forceinline__ void dc_rows(const float* __restrict__ s, float* __restrict__ d, int r0, int r1, int c0, int c1, int PW, int gx0, const DcArgs& a, int tid) {
   const int cols = c1 - c0, n = (r1 - r0) * cols, R = a.radius;
   const float inv = 1.0f / (float)cols;
   for (int e = tid; e < n; e += DC_THREADS) {
     int r, c;
-    dc_split(e, cols, inv, r, c);
+    tdk_split_rc(e, cols, inv, r, c);
     const int sy = r0 + r, sx = c0 + c;
     const float* p = s + sy * PW + (min(max(gx0 + sx, 0), a.width - 1) - gx0);
     float h = a.w[0] * p[0];
@@ -103,7 +94,7 @@ __device__ __forceinline__ void dc_cols(const float* __restrict__ h, float* __re
   const float inv = 1.0f / (float)cols;
   for (int e = tid; e < n; e += DC_THREADS) {
     int r, c;
-    dc_split(e, cols, inv, r, c);
+    tdk_split_rc(e, cols, inv, r, c);
     const int sy = r0 + r, sx = c0 + c;
     const float* p = h + (min(max(gy0 + sy, 0), a.height - 1) - gy0) * PW + sx;
     float v = a.w[0] * p[0];
@@ -131,7 +122,7 @@ __device__ __forceinline__ void dc_rows4(const float* __restrict__ s, float* __r
   const float inv = 1.0f / (float)groups;
   for (int e = tid; e < n; e += DC_THREADS) {
     int r, g;
-    dc_split(e, groups, inv, r, g);
+    tdk_split_rc(e, groups, inv, r, g);
     const int x = c0a + 4 * g, row = (r0 + r) * PW;
     float v[4 * NCH];
 #pragma unroll
@@ -159,7 +150,7 @@ __device__ __forceinline__ void dc_cols4(const float* __restrict__ h, float* __r
   const float inv = 1.0f / (float)groups;
   for (int e = tid; e < n; e += DC_THREADS) {
     int r, g;
-    dc_split(e, groups, inv, r, g);
+    tdk_split_rc(e, groups, inv, r, g);
     const int i = (r0 + r) * PW + c0a + 4 * g;
     const float4* p = reinterpret_cast<const float4*>(h + i);
     const int row4 = PW / 4;
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(DC_THREADS) void deconv_kernel(const T* __restrict_
 #pragma unroll
       for (int k = 0; k < DC_STAGE; k++) {
         int sy, sx;
-        dc_split(min(e0 + k * DC_THREADS, n - 1), PW, inv, sy, sx);
+        tdk_split_rc(min(e0 + k * DC_THREADS, n - 1), PW, inv, sy, sx);
         const size_t p = (size_t)min(max(gy0 + sy, 0), H - 1) * W + min(max(gx0 + sx, 0), W - 1);
 #pragma unroll
         for (int c = 0; c < C; c++) x[k][c] = ld(src, C * p + c);
@@ -217,8 +208,8 @@ __global__ __launch_bounds__(DC_THREADS) void deconv_kernel(const T* __restrict_
       for (int k = 0; k < DC_STAGE; k++) {
         const int e = e0 + k * DC_THREADS;
         float y;
-        if constexpr (C == 3) y = dc_pos((a.l0 * x[k][0] + a.l1 * x[k][1]) + a.l2 * x[k][2]);
-        else y = dc_pos(x[k][0]);
+        if constexpr (C == 3) y = tdk_pos((a.l0 * x[k][0] + a.l1 * x[k][1]) + a.l2 * x[k][2]);
+        else y = tdk_pos(x[k][0]);
         const float o = fmaxf(y, DC_TINY);
         if (e < n) lds.o[e] = o, lds.u[e] = first ? o : v[k];
       }
@@ -342,12 +333,11 @@ size_t dc_workspace_bytes(int width, int height, int launches) {
   const int planes = dc_plane_count(launches);
   return planes == 0 ? 0 : (size_t)planes * dc_plane_floats(width, height) * sizeof(float) + DC_WS_ALIGN;
 }
-bool dc_size_ok(int width, int height) { return width >= 1 && height >= 1 && width <= DC_MAX_SIZE && height <= DC_MAX_SIZE; }
 
 // 0: fine; otherwise which argument is wrong (messages in tdk_deconv).  *fused receives F.
 int dc_check(int channels, int dtype, int radius, int flags, int* fused) {
   if (channels != 1 && channels != 3) return 1;
-  if (dtype != TDK_F32 && dtype != TDK_F16) return 2;
+  if (!tdk_float_dtype_ok(dtype)) return 2;
   if (radius < 1 || radius > DC_MAX_R) return 3;
   if (flags < 0 || (flags & ~(TDK_DECONV_MASK | TDK_DECONV_FUSE_MASK)) != 0) return 4;
   const int forced = (flags & TDK_DECONV_FUSE_MASK) >> TDK_DECONV_FUSE_SHIFT;
@@ -385,25 +375,13 @@ int dc_dispatch(int fused, const void* src, void* dst, float* mask_out, float* p
 TDK_EXPORT int tdk_deconv_abi_version(void) { return TDK_DECONV_ABI_VERSION; }
 
 TDK_EXPORT int tdk_deconv_weights(float sigma, float* weights, int* radius) {
-  TDK_REQUIRE(weights && radius, "tdk_deconv_weights: null pointer");
-  TDK_REQUIRE(sigma >= 0.3f && sigma <= 2.0f, "tdk_deconv_weights: sigma must lie in [0.3, 2]");
-  const double s = (double)sigma;
-  const int R = (int)ceil(3.0 * s);
-  double w[DC_MAX_R + 1] = {1.0}, tail = 0.0;
-  for (int k = 1; k <= R; k++) {
-    w[k] = exp(-(double)(k * k) / (2.0 * s * s));
-    tail += w[k];
-  }
-  const double norm = w[0] + 2.0 * tail;
-  for (int k = 0; k <= DC_MAX_R; k++) weights[k] = k <= R ? (float)(w[k] / norm) : 0.0f;
-  *radius = R;
-  return TDK_OK;
+  return tdk_gaussian_taps("tdk_deconv_weights", sigma, 0.3f, 2.0f, DC_MAX_R, weights, radius);
 }
 
 TDK_EXPORT int tdk_deconv_fused_iterations(int radius) { return radius >= 1 && radius <= DC_MAX_R ? dc_default_fused(radius) : 0; }
 
 TDK_EXPORT size_t tdk_deconv_workspace_bytes(int width, int height, int radius, int iterations) {
-  if (!dc_size_ok(width, height) || radius < 1 || radius > DC_MAX_R || iterations < 0 || iterations > TDK_DECONV_MAX_ITERATIONS) return 0;
+  if (!tdk_frame_size_ok(width, height) || radius < 1 || radius > DC_MAX_R || iterations < 0 || iterations > TDK_DECONV_MAX_ITERATIONS) return 0;
   return dc_workspace_bytes(width, height, dc_launch_count(iterations, dc_default_fused(radius)));
 }
 
@@ -418,7 +396,7 @@ TDK_EXPORT int tdk_deconv(const void* src, void* dst, float* mask_out, void* wor
   TDK_REQUIRE(src && dst, "tdk_deconv: null pointer (src or dst)");
   TDK_REQUIRE(weights, "tdk_deconv: null pointer (weights)");
   TDK_REQUIRE(luma, "tdk_deconv: null pointer (luma)");
-  TDK_REQUIRE(dc_size_ok(width, height), "tdk_deconv: frame size %dx%d outside 1..%d", width, height, DC_MAX_SIZE);
+  TDK_REQUIRE(tdk_frame_size_ok(width, height), "tdk_deconv: frame size %dx%d outside 1..%d", width, height, TDK_FRAME_MAX_SIZE);
   int fused = 0;
   const int bad = dc_check(channels, dtype, radius, flags, &fused);
   TDK_REQUIRE(bad != 1, "tdk_deconv: channels must be 1 or 3, got %d", channels);
@@ -427,12 +405,14 @@ TDK_EXPORT int tdk_deconv(const void* src, void* dst, float* mask_out, void* wor
   TDK_REQUIRE(bad != 4, "tdk_deconv: flags must be TDK_DECONV_MASK and a fused count in bits 8..11, the other bits are reserved, got %d", flags);
   TDK_REQUIRE(bad != 5 && dc_max_radius(fused) != 0, "tdk_deconv: the fused count of flags must be 0, 1, 2 or 4 and take the radius (R <= 6, 4, 2), got %d at radius %d",
               (flags & TDK_DECONV_FUSE_MASK) >> TDK_DECONV_FUSE_SHIFT, radius);
-  for (int k = 0; k <= radius; k++) TDK_REQUIRE(isfinite(weights[k]) && weights[k] >= 0.0f, "tdk_deconv: weights[%d] must be finite and >= 0", k);
+  const int bad_tap = tdk_first_bad_weight(weights, radius + 1);
+  TDK_REQUIRE(bad_tap < 0, "tdk_deconv: weights[%d] must be finite and >= 0", bad_tap);
   TDK_REQUIRE(iterations >= 0 && iterations <= TDK_DECONV_MAX_ITERATIONS, "tdk_deconv: iterations must be 0..%d, got %d", TDK_DECONV_MAX_ITERATIONS, iterations);
   const bool mask = (flags & TDK_DECONV_MASK) != 0;
   TDK_REQUIRE(!mask || (isfinite(threshold) && threshold > 0.0f), "tdk_deconv: threshold must be finite and > 0");
   TDK_REQUIRE(max_gain >= 1.0f && max_gain <= DC_MAX_GAIN, "tdk_deconv: max_gain must lie in [1, %g]", (double)DC_MAX_GAIN);
-  for (int k = 0; k < 3; k++) TDK_REQUIRE(isfinite(luma[k]) && luma[k] >= 0.0f, "tdk_deconv: luma weights must be finite and >= 0 (luma[%d])", k);
+  const int bad_luma = tdk_first_bad_weight(luma, 3);
+  TDK_REQUIRE(bad_luma < 0, "tdk_deconv: luma weights must be finite and >= 0 (luma[%d])", bad_luma);
   TDK_REQUIRE(tdk_aligned(mask_out, 4), "tdk_deconv: mask_out must be aligned to 4 bytes");
   const int launches = dc_launch_count(iterations, fused);
   const size_t ws_bytes = dc_workspace_bytes(width, height, launches);
@@ -454,11 +434,10 @@ TDK_EXPORT int tdk_deconv(const void* src, void* dst, float* mask_out, void* wor
   a.bits = (mask ? DC_MASK : 0) | (iterations == 0 ? DC_COPY : 0);
   float* planes = ws_bytes == 0 ? nullptr : reinterpret_cast<float*>(tdk_align_up(reinterpret_cast<uintptr_t>(workspace), DC_WS_ALIGN));
   // a thread's four pixels as whole vectors: rows must hold whole groups and start on the vector's alignment
-  const bool rows4 = width % DC_PIX == 0;
-  if (rows4 && tdk_aligned(src, 4 * esz)) a.bits |= DC_VEC_IN;
-  if (rows4 && tdk_aligned(dst, 4 * esz)) a.bits |= DC_VEC_OUT;
-  if (rows4) a.bits |= DC_VEC_U;   // (the planes start on 16 bytes)
-  if (rows4 && tdk_aligned(mask_out, 16)) a.bits |= DC_VEC_M;
+  if (tdk_vec4_ok(width, src, 4 * esz)) a.bits |= DC_VEC_IN;
+  if (tdk_vec4_ok(width, dst, 4 * esz)) a.bits |= DC_VEC_OUT;
+  if (width % DC_PIX == 0) a.bits |= DC_VEC_U;   // (the planes start on 16 bytes)
+  if (tdk_vec4_ok(width, mask_out, 16)) a.bits |= DC_VEC_M;
   hipStream_t st = tdk_stream(stream);
   const size_t plane_floats = dc_plane_floats(width, height);
   if (dtype == TDK_F32) {

@@ -35,7 +35,6 @@ namespace {
 constexpr int DF_THREADS = 256;
 constexpr int DF_T = TDK_DEFRINGE_TILE, DF_PIX = 4, DF_GROUPS = DF_T / DF_PIX;   // 8 threads per tile row, 32 rows
 constexpr int DF_MAX_R = TDK_DEFRINGE_MAX_RADIUS, DF_MAX_S = TDK_DEFRINGE_MAX_SAMPLE_RADIUS;
-constexpr int DF_MAX_SIZE = 65535;
 constexpr int DF_MAX_WG = TDK_DEFRINGE_MAX_GROUPS;
 constexpr size_t DF_WS_ALIGN = 16;
 constexpr float DF_SCALE = (float)TDK_DEFRINGE_STAT_SCALE, DF_CAP = (float)TDK_DEFRINGE_STAT_CAP;
@@ -69,18 +68,11 @@ enum : int {
   DF_VEC_E = 8,                   // ... of four floats for the workspace plane of E
 };
 
-__device__ __forceinline__ float df_pos(float v) { return v > 0.0f ? v : 0.0f; }
-
 template <bool SQRT> __device__ __forceinline__ float df_work(float x) {
-  const float p = df_pos(x);
+  const float p = tdk_pos(x);
   return SQRT ? sqrtf(p) : p;
 }
 
-// e-th position of a region of `cols` columns in row order; inv = 1 / cols.  The quotient is never near an integer.
-__device__ __forceinline__ void df_split(int e, int cols, float inv, int& r, int& c) {
-  r = (int)(((float)e + 0.5f) * inv);
-  c = e - r * cols;
-}
 
 // the sum of a value over the workgroup, the same in every thread; `part` is one word per wave
 __device__ __forceinline__ unsigned long long df_block_sum(unsigned long long v, unsigned long long* part) {
@@ -171,7 +163,7 @@ __global__ __launch_bounds__(DF_THREADS) void defringe_edge_kernel(const T* __re
     // 1. Cb, Cr of the clamped pixel
     for (int e = tid; e < PW * PW; e += DF_THREADS) {
       int r, c;
-      df_split(e, PW, inv_pw, r, c);
+      tdk_split_rc(e, PW, inv_pw, r, c);
       const int gy = min(max(y0 - R + r, 0), H - 1), gx = min(max(x0 - R + c, 0), W - 1);
       const size_t i = ((size_t)gy * W + gx) * 3;
       const float tr = df_work<SQRT>(ld(src, i)), tg = df_work<SQRT>(ld(src, i + 1)), tb = df_work<SQRT>(ld(src, i + 2));
@@ -291,7 +283,7 @@ __global__ __launch_bounds__(DF_THREADS) void defringe_correct_kernel(const T* _
     const float inv_pw = 1.0f / (float)PW;
     for (int e = tid; e < PW * PW; e += DF_THREADS) {
       int r, c;
-      df_split(e, PW, inv_pw, r, c);
+      tdk_split_rc(e, PW, inv_pw, r, c);
       const int gy = min(max(y0 - S + r, 0), H - 1), gx = min(max(x0 - S + c, 0), W - 1);
       const size_t p = (size_t)gy * W + gx;
       const float t_r = df_work<SQRT>(ld(src, p * 3)), t_g = df_work<SQRT>(ld(src, p * 3 + 1)), t_b = df_work<SQRT>(ld(src, p * 3 + 2));
@@ -353,8 +345,6 @@ __global__ __launch_bounds__(DF_THREADS) void defringe_correct_kernel(const T* _
   }
 }
 
-bool df_size_ok(int width, int height) { return width >= 1 && height >= 1 && width <= DF_MAX_SIZE && height <= DF_MAX_SIZE; }
-bool df_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
 bool df_flags_ok(int flags) {
   if (flags & ~(TDK_DEFRINGE_LINEAR | TDK_DEFRINGE_STATIC | TDK_DEFRINGE_GROUPS_MASK)) return false;
   return ((flags & TDK_DEFRINGE_GROUPS_MASK) >> TDK_DEFRINGE_GROUPS_SHIFT) <= DF_MAX_WG;
@@ -378,25 +368,13 @@ int df_run(const void* src, void* dst, unsigned char* mask_out, float* edge_out,
 TDK_EXPORT int tdk_defringe_abi_version(void) { return TDK_DEFRINGE_ABI_VERSION; }
 
 TDK_EXPORT int tdk_defringe_weights(float sigma, float* weights, int* radius) {
-  TDK_REQUIRE(weights && radius, "tdk_defringe_weights: null pointer");
-  TDK_REQUIRE(sigma >= 0.5f && sigma <= 4.0f, "tdk_defringe_weights: sigma must lie in [0.5, 4]");
-  const double s = (double)sigma;
-  const int R = (int)ceil(3.0 * s);
-  double w[DF_MAX_R + 1] = {1.0}, tail = 0.0;
-  for (int k = 1; k <= R; k++) {
-    w[k] = exp(-(double)(k * k) / (2.0 * s * s));
-    tail += w[k];
-  }
-  const double norm = w[0] + 2.0 * tail;
-  for (int k = 0; k <= DF_MAX_R; k++) weights[k] = k <= R ? (float)(w[k] / norm) : 0.0f;
-  *radius = R;
-  return TDK_OK;
+  return tdk_gaussian_taps("tdk_defringe_weights", sigma, 0.5f, 4.0f, DF_MAX_R, weights, radius);
 }
 
-TDK_EXPORT size_t tdk_defringe_workspace_bytes(int width, int height) { return df_size_ok(width, height) ? df_workspace_bytes(width, height) : 0; }
+TDK_EXPORT size_t tdk_defringe_workspace_bytes(int width, int height) { return tdk_frame_size_ok(width, height) ? df_workspace_bytes(width, height) : 0; }
 
 TDK_EXPORT size_t tdk_defringe_lds_bytes(int dtype, int radius, int sample_radius, int flags) {
-  if (!df_dtype_ok(dtype) || radius < 1 || radius > DF_MAX_R || sample_radius < 1 || sample_radius > DF_MAX_S || !df_flags_ok(flags)) return 0;
+  if (!tdk_float_dtype_ok(dtype) || radius < 1 || radius > DF_MAX_R || sample_radius < 1 || sample_radius > DF_MAX_S || !df_flags_ok(flags)) return 0;
   return sizeof(DfEdgeLds) > sizeof(DfCorrectLds) ? sizeof(DfEdgeLds) : sizeof(DfCorrectLds);
 }
 
@@ -406,10 +384,11 @@ TDK_EXPORT int tdk_defringe(const void* src, void* dst, unsigned char* mask_out,
   TDK_REQUIRE(src && dst, "tdk_defringe: null pointer (src or dst)");
   TDK_REQUIRE(weights, "tdk_defringe: null pointer (weights)");
   TDK_REQUIRE(workspace, "tdk_defringe: null pointer (workspace)");
-  TDK_REQUIRE(df_size_ok(width, height), "tdk_defringe: frame size %dx%d outside 1..%d", width, height, DF_MAX_SIZE);
-  TDK_REQUIRE(df_dtype_ok(dtype), "tdk_defringe: unsupported dtype tag %d", dtype);
+  TDK_REQUIRE(tdk_frame_size_ok(width, height), "tdk_defringe: frame size %dx%d outside 1..%d", width, height, TDK_FRAME_MAX_SIZE);
+  TDK_REQUIRE(tdk_float_dtype_ok(dtype), "tdk_defringe: unsupported dtype tag %d", dtype);
   TDK_REQUIRE(radius >= 1 && radius <= DF_MAX_R, "tdk_defringe: radius must be 1..%d, got %d", DF_MAX_R, radius);
-  for (int k = 0; k <= radius; k++) TDK_REQUIRE(isfinite(weights[k]) && weights[k] >= 0.0f, "tdk_defringe: weights[%d] must be finite and >= 0", k);
+  const int bad_tap = tdk_first_bad_weight(weights, radius + 1);
+  TDK_REQUIRE(bad_tap < 0, "tdk_defringe: weights[%d] must be finite and >= 0", bad_tap);
   TDK_REQUIRE(sample_radius >= 1 && sample_radius <= DF_MAX_S, "tdk_defringe: sample_radius must be 1..%d, got %d", DF_MAX_S, sample_radius);
   TDK_REQUIRE(isfinite(strength) && strength >= 0.0f, "tdk_defringe: strength must be finite and >= 0");
   TDK_REQUIRE(isfinite(floor) && floor > 0.0f, "tdk_defringe: floor must be finite and > 0");
@@ -438,10 +417,9 @@ TDK_EXPORT int tdk_defringe(const void* src, void* dst, unsigned char* mask_out,
   a.groups = tiles < limit ? (int)tiles : limit;
   a.bits = (flags & TDK_DEFRINGE_STATIC) ? DF_STATIC : 0;
   // a thread's four pixels as whole vectors: rows must hold whole groups and start on the vector's alignment
-  const bool rows4 = width % DF_PIX == 0;
-  if (rows4 && tdk_aligned(src, 4 * esz)) a.bits |= DF_VEC_IN;
-  if (rows4 && tdk_aligned(dst, 4 * esz)) a.bits |= DF_VEC_OUT;
-  if (rows4) a.bits |= DF_VEC_E;   // (the plane starts on 16 bytes)
+  if (tdk_vec4_ok(width, src, 4 * esz)) a.bits |= DF_VEC_IN;
+  if (tdk_vec4_ok(width, dst, 4 * esz)) a.bits |= DF_VEC_OUT;
+  if (width % DF_PIX == 0) a.bits |= DF_VEC_E;   // (the plane starts on 16 bytes)
   float* eplane = reinterpret_cast<float*>(tdk_align_up(reinterpret_cast<uintptr_t>(workspace), DF_WS_ALIGN));
   unsigned long long* records = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(eplane) + df_plane_bytes(width, height));
   const bool linear = (flags & TDK_DEFRINGE_LINEAR) != 0;

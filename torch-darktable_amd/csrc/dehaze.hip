@@ -31,7 +31,6 @@ namespace {
 
 constexpr int DH_THREADS = 256;
 constexpr int DH_SEL_THREADS = 1024;
-constexpr int DH_MAX_SIZE = 65535;
 constexpr int DH_RD = TDK_DEHAZE_MAX_DARK_RADIUS, DH_RG = TDK_DEHAZE_MAX_RADIUS;
 constexpr int DH_BAND = 16;                        // pixel rows of a wave of dh_cells
 constexpr int DH_CT = 32;                          // dh_dark, dh_coeff: a tile of DH_CT x DH_CT cells
@@ -54,8 +53,7 @@ struct DhArgs {
   float w0, w1, w2;
 };
 
-__device__ __forceinline__ float dh_pos(float v) { return v > 0.0f ? v : 0.0f; }
-__device__ __forceinline__ float dh_lum(const DhArgs& a, float r, float g, float b) { return dh_pos((a.w0 * r + a.w1 * g) + a.w2 * b); }
+__device__ __forceinline__ float dh_lum(const DhArgs& a, float r, float g, float b) { return tdk_pos((a.w0 * r + a.w1 * g) + a.w2 * b); }
 
 // PX pixels of a row from column x0 on as v[3 * i + c]; columns past the row's end repeat its last pixel
 template <typename T> __device__ __forceinline__ void dh_load(const T* __restrict__ row, int x0, int w, float* v);
@@ -180,7 +178,7 @@ __global__ __launch_bounds__(DH_THREADS) void dh_cells(const T* __restrict__ src
 #pragma unroll
         for (int i = 0; i < SUB; i++) {
           const float* px = v + 3 * (c * SUB + i);
-          p[0][i] = dh_pos(px[0]), p[1][i] = dh_pos(px[1]), p[2][i] = dh_pos(px[2]);
+          p[0][i] = tdk_pos(px[0]), p[1][i] = tdk_pos(px[1]), p[2][i] = tdk_pos(px[2]);
           p[3][i] = dh_lum(a, px[0], px[1], px[2]);
         }
 #pragma unroll
@@ -424,7 +422,7 @@ __global__ __launch_bounds__(DH_THREADS) void dh_coeff(const float* __restrict__
     }
     const float ml = s1 * a.inv, mt = s2 * a.inv;
     const float cov = s3 * a.inv - ml * mt;
-    const float var = dh_pos(s4 * a.inv - ml * ml);
+    const float var = tdk_pos(s4 * a.inv - ml * ml);
     const float ga = cov / (var + a.eps);
     const size_t o = (size_t)cy * a.cw + cx;
     ca[o] = ga;
@@ -511,7 +509,7 @@ __global__ __launch_bounds__(DH_THREADS) void dh_apply(const T* __restrict__ src
       m[i] = fminf(fmaxf(au * lum + bu, a.floor), 1.0f);
       const float rt = 1.0f / m[i];
 #pragma unroll
-      for (int c = 0; c < 3; c++) v[3 * i + c] = dh_pos((v[3 * i + c] - amb[c]) * rt + amb[c]);
+      for (int c = 0; c < 3; c++) v[3 * i + c] = tdk_pos((v[3 * i + c] - amb[c]) * rt + amb[c]);
       // The sum is a float32 value and the store rounds that to binary16: two roundings.  Left alone, the compiler may fold the add
       // and the conversion into one v_fma_mixlo_f16, which rounds once: the empty asm keeps the float32 sum a value of its own.
       if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(v[3 * i]), "+v"(v[3 * i + 1]), "+v"(v[3 * i + 2]));
@@ -522,7 +520,6 @@ __global__ __launch_bounds__(DH_THREADS) void dh_apply(const T* __restrict__ src
 }
 
 bool dh_cell_ok(int cell) { return cell == 2 || cell == 4 || cell == 8 || cell == 16; }
-bool dh_size_ok(int width, int height) { return width >= 1 && height >= 1 && width <= DH_MAX_SIZE && height <= DH_MAX_SIZE; }
 size_t dh_cells_of(int width, int height, int cell) { return (size_t)tdk_div_up(width, cell) * tdk_div_up(height, cell); }
 
 // Run a statement with the cell size S as a constant; the caller has checked `cell`.
@@ -564,8 +561,8 @@ int dh_check_common(const char* who, const void* src, const void* workspace, con
   TDK_REQUIRE(src, "%s: null pointer (src)", who);
   TDK_REQUIRE(workspace, "%s: null pointer (workspace)", who);
   TDK_REQUIRE(ambient, "%s: null pointer (ambient)", who);
-  TDK_REQUIRE(dh_size_ok(width, height), "%s: frame size %dx%d outside 1..%d", who, width, height, DH_MAX_SIZE);
-  TDK_REQUIRE(dtype == TDK_F32 || dtype == TDK_F16, "%s: unsupported dtype tag %d", who, dtype);
+  TDK_REQUIRE(tdk_frame_size_ok(width, height), "%s: frame size %dx%d outside 1..%d", who, width, height, TDK_FRAME_MAX_SIZE);
+  TDK_REQUIRE(tdk_float_dtype_ok(dtype), "%s: unsupported dtype tag %d", who, dtype);
   TDK_REQUIRE(dh_cell_ok(cell), "%s: cell must be 2, 4, 8 or 16, got %d", who, cell);
   TDK_REQUIRE(dh_cells_of(width, height, cell) <= (size_t)TDK_DEHAZE_MAX_CELLS, "%s: the grid of %zu cells is larger than %d", who, dh_cells_of(width, height, cell),
               TDK_DEHAZE_MAX_CELLS);
@@ -580,12 +577,12 @@ int dh_check_common(const char* who, const void* src, const void* workspace, con
 TDK_EXPORT int tdk_dehaze_abi_version(void) { return TDK_DEHAZE_ABI_VERSION; }
 
 TDK_EXPORT size_t tdk_dehaze_workspace_bytes(int width, int height, int cell) {
-  if (!dh_size_ok(width, height) || !dh_cell_ok(cell) || dh_cells_of(width, height, cell) > (size_t)TDK_DEHAZE_MAX_CELLS) return 0;
+  if (!tdk_frame_size_ok(width, height) || !dh_cell_ok(cell) || dh_cells_of(width, height, cell) > (size_t)TDK_DEHAZE_MAX_CELLS) return 0;
   return (size_t)TDK_DEHAZE_PLANES * dh_cells_of(width, height, cell) * sizeof(float) + DH_WS_ALIGN;
 }
 
 TDK_EXPORT size_t tdk_dehaze_lds_bytes(int dtype, int cell, int dark_radius, int radius) {
-  if ((dtype != TDK_F32 && dtype != TDK_F16) || !dh_cell_ok(cell) || dark_radius < 0 || dark_radius > DH_RD || radius < 0 || radius > DH_RG) return 0;
+  if (!tdk_float_dtype_ok(dtype) || !dh_cell_ok(cell) || dark_radius < 0 || dark_radius > DH_RD || radius < 0 || radius > DH_RG) return 0;
   size_t most = 0;
   DH_DISPATCH_CELL(cell, S, most = dh_apply_lds<S>());
   for (size_t other : {sizeof(DhCoeffLds), sizeof(DhDarkLds), sizeof(DhSelectLds)}) most = other > most ? other : most;
@@ -623,7 +620,8 @@ TDK_EXPORT int tdk_dehaze(const void* src, void* dst, float* transmission_out, v
   TDK_REQUIRE(eps > 0.0f && isfinite(eps), "%s: eps must be finite and > 0", who);
   TDK_REQUIRE(strength >= 0.0f && strength <= 1.0f, "%s: strength must be in 0..1", who);
   TDK_REQUIRE(floor >= 0x1p-6f && floor <= 1.0f, "%s: floor must be in 2^-6..1", who);
-  for (int k = 0; k < 3; k++) TDK_REQUIRE(isfinite(weights[k]) && weights[k] >= 0.0f, "%s: weights must be finite and >= 0 (weights[%d])", who, k);
+  const int bad_weight = tdk_first_bad_weight(weights, 3);
+  TDK_REQUIRE(bad_weight < 0, "%s: weights must be finite and >= 0 (weights[%d])", who, bad_weight);
   TDK_REQUIRE(tdk_aligned(transmission_out, 4), "%s: transmission_out must be aligned to 4 bytes", who);
   const size_t n = (size_t)width * height, frame_bytes = n * 3 * tdk_dtype_bytes(dtype), plane_bytes = n * sizeof(float);
   const size_t ws_bytes = tdk_dehaze_workspace_bytes(width, height, cell), amb_bytes = 4 * sizeof(float);

@@ -103,7 +103,6 @@ __device__ __forceinline__ void fm_store48(uint8_t* p, const float v[FM_EL]) {
 }
 
 // ---- the steps on one pixel
-__device__ __forceinline__ float fm_pos(float v) { return v > 0.0f ? v : 0.0f; }
 __device__ __forceinline__ float fm_xmin() { return __uint_as_float(0x35800000u); }    // 2^-20
 __device__ __forceinline__ float fm_xmax() { return __uint_as_float(0x457FFFFFu); }    // the largest float32 below 2^12
 __device__ __forceinline__ float fm_below_one() { return __uint_as_float(0x3F7FFFFFu); }   // 1 - 2^-24
@@ -119,7 +118,7 @@ __device__ __forceinline__ int fm_index(float clamped, int ev_min, float& f) {
 
 // step 6
 __device__ __forceinline__ float fm_encode(float o, const float2* g, float g0) {
-  const float oc = fminf(fm_pos(o), fm_below_one());
+  const float oc = fminf(tdk_pos(o), fm_below_one());
   const float lo = __uint_as_float(0x37800000u);   // 2^-16
   float f;
   const int i = fm_index(fmaxf(oc, lo), TDK_FILMIC_ENC_EV_MIN, f);
@@ -130,7 +129,7 @@ __device__ __forceinline__ float fm_encode(float o, const float2* g, float g0) {
 }
 
 template <int NORM> __device__ __forceinline__ void fm_pixel(float& x0, float& x1, float& x2, float e, const float4* td, const float2* g, float g0, const FilmicArgs& a) {
-  const float p0 = fminf(fm_pos(x0 * e), fm_xmax()), p1 = fminf(fm_pos(x1 * e), fm_xmax()), p2 = fminf(fm_pos(x2 * e), fm_xmax());
+  const float p0 = fminf(tdk_pos(x0 * e), fm_xmax()), p1 = fminf(tdk_pos(x1 * e), fm_xmax()), p2 = fminf(tdk_pos(x2 * e), fm_xmax());
   float o0, o1, o2;
   if constexpr (NORM == TDK_FILMIC_NONE) {
     const float p[3] = {p0, p1, p2};
@@ -276,11 +275,12 @@ TDK_EXPORT int tdk_filmic(const void* src, void* dst, const float* curve, const 
   TDK_REQUIRE(exposure, "tdk_filmic: null pointer (exposure)");
   TDK_REQUIRE(weights, "tdk_filmic: null pointer (weights)");
   TDK_REQUIRE(npix >= 0, "tdk_filmic: npix must be >= 0, got %lld", (long long)npix);
-  TDK_REQUIRE(src_dtype == TDK_F32 || src_dtype == TDK_F16, "tdk_filmic: unsupported source dtype tag %d (float32 or binary16)", src_dtype);
+  TDK_REQUIRE(tdk_float_dtype_ok(src_dtype), "tdk_filmic: unsupported source dtype tag %d (float32 or binary16)", src_dtype);
   TDK_REQUIRE(dst_dtype == TDK_F32 || dst_dtype == TDK_F16 || dst_dtype == TDK_U8, "tdk_filmic: unsupported destination dtype tag %d", dst_dtype);
   TDK_REQUIRE(norm == TDK_FILMIC_MAX || norm == TDK_FILMIC_LUMA || norm == TDK_FILMIC_POWER || norm == TDK_FILMIC_NONE,
               "tdk_filmic: norm must be TDK_FILMIC_MAX, _LUMA, _POWER or _NONE, got %d", norm);
-  for (int c = 0; c < 3; c++) TDK_REQUIRE(isfinite(weights[c]) && weights[c] >= 0.0f, "tdk_filmic: weights[%d] must be finite and >= 0", c);
+  const int bad_weight = tdk_first_bad_weight(weights, 3);
+  TDK_REQUIRE(bad_weight < 0, "tdk_filmic: weights[%d] must be finite and >= 0", bad_weight);
   TDK_REQUIRE(flags == 0, "tdk_filmic: flags is reserved and must be 0, got %d", flags);
   const size_t ssz = tdk_dtype_bytes(src_dtype), dsz = tdk_dtype_bytes(dst_dtype);
   TDK_REQUIRE(tdk_aligned(src, ssz), "tdk_filmic: src must be aligned to its elements (%zu bytes)", ssz);

@@ -229,7 +229,6 @@ bool lm_size_ok(int width, int height) {
   return width >= TDK_LMMSE_MIN_SIZE && height >= TDK_LMMSE_MIN_SIZE && width <= TDK_LMMSE_MAX_SIZE && height <= TDK_LMMSE_MAX_SIZE;
 }
 bool lm_pattern_ok(uint32_t p) { return p == TDK_PATTERN_RGGB || p == TDK_PATTERN_BGGR || p == TDK_PATTERN_GRBG || p == TDK_PATTERN_GBRG; }
-bool lm_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
 bool lm_flags_ok(int flags) { return (flags & ~TDK_LMMSE_LINEAR) == 0; }
 
 template <typename TI, typename TO, bool SQRT>
@@ -251,22 +250,22 @@ int lm_domain(bool linear, const void* src, void* dst, int width, int height, ui
 TDK_EXPORT int tdk_lmmse_abi_version(void) { return TDK_LMMSE_ABI_VERSION; }
 
 TDK_EXPORT size_t tdk_lmmse_lds_bytes(int src_dtype, int dst_dtype, int flags) {
-  return lm_dtype_ok(src_dtype) && lm_dtype_ok(dst_dtype) && lm_flags_ok(flags) ? sizeof(LmLds) : 0;
+  return tdk_float_dtype_ok(src_dtype) && tdk_float_dtype_ok(dst_dtype) && lm_flags_ok(flags) ? sizeof(LmLds) : 0;
 }
 
 TDK_EXPORT int tdk_lmmse(const void* src, void* dst, int width, int height, uint32_t pattern, int src_dtype, int dst_dtype, int flags, tdk_stream_t stream) {
   TDK_REQUIRE(src && dst, "tdk_lmmse: null pointer (src or dst)");
   TDK_REQUIRE(lm_size_ok(width, height), "tdk_lmmse: frame size %dx%d outside %d..%d", width, height, TDK_LMMSE_MIN_SIZE, TDK_LMMSE_MAX_SIZE);
   TDK_REQUIRE(lm_pattern_ok(pattern), "tdk_lmmse: pattern 0x%08x is none of the four Bayer patterns", (unsigned)pattern);
-  TDK_REQUIRE(lm_dtype_ok(src_dtype), "tdk_lmmse: unsupported dtype tag %d (src)", src_dtype);
-  TDK_REQUIRE(lm_dtype_ok(dst_dtype), "tdk_lmmse: unsupported dtype tag %d (dst)", dst_dtype);
+  TDK_REQUIRE(tdk_float_dtype_ok(src_dtype), "tdk_lmmse: unsupported dtype tag %d (src)", src_dtype);
+  TDK_REQUIRE(tdk_float_dtype_ok(dst_dtype), "tdk_lmmse: unsupported dtype tag %d (dst)", dst_dtype);
   TDK_REQUIRE(lm_flags_ok(flags), "tdk_lmmse: flags must be 0 or TDK_LMMSE_LINEAR, the other bits are reserved, got %d", flags);
   const size_t n = (size_t)width * height, src_bytes = n * tdk_dtype_bytes(src_dtype), dst_bytes = 3 * n * tdk_dtype_bytes(dst_dtype);
   TDK_REQUIRE(tdk_disjoint(src, src_bytes, dst, dst_bytes), "tdk_lmmse: src and dst overlap (every output reads its neighbours)");
 
   int bits = cfa_color(0, 0, pattern) == 1 ? 0 : LM_GREEN_ODD;
   // a thread's four pixels as one vector: rows must hold whole groups and start on the vector's alignment
-  if (width % LM_PIX == 0 && tdk_aligned(dst, 4 * tdk_dtype_bytes(dst_dtype))) bits |= LM_VEC_OUT;
+  if (tdk_vec4_ok(width, dst, 4 * tdk_dtype_bytes(dst_dtype))) bits |= LM_VEC_OUT;
   const bool linear = (flags & TDK_LMMSE_LINEAR) != 0;
   hipStream_t st = tdk_stream(stream);
   if (src_dtype == TDK_F32) {

@@ -34,7 +34,6 @@ namespace {
 constexpr int SH_THREADS = 256;
 constexpr int SH_TW = 32, SH_TH = 32, SH_PIX = 4, SH_GROUPS = SH_TW / SH_PIX;   // 8 threads per tile row, 32 rows
 constexpr int SH_MAX_R = TDK_SHARPEN_MAX_RADIUS;
-constexpr int SH_MAX_SIZE = 65535;
 constexpr float SH_MAX_AMOUNT = 16.0f;
 constexpr size_t SH_LDS_LIMIT = 64 * 1024;   // the dynamic-LDS size a kernel gets without raising its limit; two workgroups per CU
 static_assert(SH_THREADS == SH_GROUPS * SH_TH, "a thread per 4 pixels of the tile");
@@ -220,19 +219,7 @@ int sh_check(int channels, int dtype, int radius, int flags) {
 TDK_EXPORT int tdk_sharpen_abi_version(void) { return TDK_SHARPEN_ABI_VERSION; }
 
 TDK_EXPORT int tdk_sharpen_weights(float sigma, float* weights, int* radius) {
-  TDK_REQUIRE(weights && radius, "tdk_sharpen_weights: null pointer");
-  TDK_REQUIRE(sigma >= 0.25f && sigma <= 4.0f, "tdk_sharpen_weights: sigma must lie in [0.25, 4]");
-  const double s = (double)sigma;
-  const int R = (int)ceil(3.0 * s);
-  double w[SH_MAX_R + 1] = {1.0}, tail = 0.0;
-  for (int k = 1; k <= R; k++) {
-    w[k] = exp(-(double)(k * k) / (2.0 * s * s));
-    tail += w[k];
-  }
-  const double norm = w[0] + 2.0 * tail;
-  for (int k = 0; k <= SH_MAX_R; k++) weights[k] = k <= R ? (float)(w[k] / norm) : 0.0f;
-  *radius = R;
-  return TDK_OK;
+  return tdk_gaussian_taps("tdk_sharpen_weights", sigma, 0.25f, 4.0f, SH_MAX_R, weights, radius);
 }
 
 TDK_EXPORT size_t tdk_sharpen_lds_bytes(int channels, int dtype, int radius, int flags) {
@@ -244,14 +231,15 @@ TDK_EXPORT int tdk_sharpen(const void* src, void* dst, int width, int height, in
                            float threshold, float overshoot, int flags, tdk_stream_t stream) {
   TDK_REQUIRE(src && dst, "tdk_sharpen: null pointer (src or dst)");
   TDK_REQUIRE(weights, "tdk_sharpen: null pointer (weights)");
-  TDK_REQUIRE(width >= 1 && height >= 1 && width <= SH_MAX_SIZE && height <= SH_MAX_SIZE, "tdk_sharpen: frame size %dx%d outside 1..%d", width, height, SH_MAX_SIZE);
+  TDK_REQUIRE(tdk_frame_size_ok(width, height), "tdk_sharpen: frame size %dx%d outside 1..%d", width, height, TDK_FRAME_MAX_SIZE);
   const int bad = sh_check(channels, dtype, radius, flags);
   TDK_REQUIRE(bad != 1, "tdk_sharpen: channels must be 1 or 3, got %d", channels);
   TDK_REQUIRE(bad != 2, "tdk_sharpen: unsupported dtype tag %d", dtype);
   TDK_REQUIRE(bad != 3, "tdk_sharpen: radius must be 1..%d, got %d", SH_MAX_R, radius);
   TDK_REQUIRE(bad != 4, "tdk_sharpen: flags must be a combination of TDK_SHARPEN_LUMA and TDK_SHARPEN_LIMIT, got %d", flags);
   TDK_REQUIRE(bad != 5, "tdk_sharpen: TDK_SHARPEN_LUMA needs three channels, got %d", channels);
-  for (int k = 0; k <= radius; k++) TDK_REQUIRE(isfinite(weights[k]) && weights[k] >= 0.0f, "tdk_sharpen: weights[%d] must be finite and >= 0", k);
+  const int bad_tap = tdk_first_bad_weight(weights, radius + 1);
+  TDK_REQUIRE(bad_tap < 0, "tdk_sharpen: weights[%d] must be finite and >= 0", bad_tap);
   TDK_REQUIRE(amount >= 0.0f && amount <= SH_MAX_AMOUNT, "tdk_sharpen: amount must lie in [0, %g]", (double)SH_MAX_AMOUNT);
   TDK_REQUIRE(isfinite(threshold) && threshold >= 0.0f, "tdk_sharpen: threshold must be finite and >= 0");
   TDK_REQUIRE(isfinite(overshoot) && overshoot >= 0.0f, "tdk_sharpen: overshoot must be finite and >= 0");
@@ -265,9 +253,8 @@ TDK_EXPORT int tdk_sharpen(const void* src, void* dst, int width, int height, in
   a.width = width, a.height = height, a.radius = radius;
   a.limit = (flags & TDK_SHARPEN_LIMIT) != 0;
   // a thread's four pixels as whole vectors of four elements: rows must hold whole groups and start on the vector's alignment
-  const bool rows4 = width % SH_PIX == 0;
-  a.vec_in = rows4 && tdk_aligned(src, 4 * esz);
-  a.vec_out = rows4 && tdk_aligned(dst, 4 * esz);
+  a.vec_in = tdk_vec4_ok(width, src, 4 * esz);
+  a.vec_out = tdk_vec4_ok(width, dst, 4 * esz);
   const bool luma = (flags & TDK_SHARPEN_LUMA) != 0;
   hipStream_t st = tdk_stream(stream);
   TDK_DISPATCH_FRAME(dtype, channels, T, C, return dispatch<T, C>(src, dst, luma, a, st));

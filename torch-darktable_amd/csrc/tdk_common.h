@@ -119,6 +119,12 @@ __host__ __device__ __forceinline__ int cfa_color(int row, int col, uint32_t pat
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 __device__ __forceinline__ float sqf(float v) { return v * v; }
+__device__ __forceinline__ float tdk_pos(float v) { return v > 0.0f ? v : 0.0f; }   // (a NaN becomes 0)
+// e-th position of a region of `cols` columns in row order; inv = 1 / cols.  The quotient is never near an integer.
+__device__ __forceinline__ void tdk_split_rc(int e, int cols, float inv, int& r, int& c) {
+  r = (int)(((float)e + 0.5f) * inv);
+  c = e - r * cols;
+}
 // reference csrc/device_math.h:80-82 and :407-409
 __device__ __forceinline__ float mixf(float a, float b, float t) { return (1.0f - t) * a + t * b; }
 __device__ __forceinline__ float lerpf(float t, float a, float b) { return a + t * (b - a); }

@@ -1,12 +1,50 @@
-// tdk_frame.h -- host-side argument helpers of the stand-alone frame operators (resample, warp, sharpen, nlmeans, rawprepare):
-// frames of TDK_F32 | TDK_F16 | TDK_U8 elements, 1 or 3 interleaved channels.  The helpers answer a question; the message of a
-// failed check stays with the entry point that reports it.
+// tdk_frame.h -- host-side argument helpers of the frame operators: resample, warp, sharpen, nlmeans, rawprepare on frames of TDK_F32 |
+// TDK_F16 | TDK_U8 elements with 1 or 3 interleaved channels, and the stages bound to one frame size (toneequal, dehaze, filmic, deconv,
+// lmmse, defringe) on TDK_F32 | TDK_F16.  The helpers answer a question; the message of a failed check stays with the entry point
+// that reports it.  The one exception is tdk_gaussian_taps, the whole body of the three tdk_*_weights entry points.
 #pragma once
 
 #include "../../include/tdk_hip_resample.h"   // TDK_U8
 #include "tdk_common.h"
 
+#include <math.h>
+
+constexpr int TDK_FRAME_MAX_SIZE = 65535;   // the largest width and height of a frame
+
+static inline bool tdk_frame_size_ok(int width, int height) { return width >= 1 && height >= 1 && width <= TDK_FRAME_MAX_SIZE && height <= TDK_FRAME_MAX_SIZE; }
+static inline bool tdk_float_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
 static inline size_t tdk_dtype_bytes(int dtype) { return dtype == TDK_F32 ? 4 : dtype == TDK_F16 ? 2 : 1; }
+
+// index of the first of n weights (blur taps, luminance weights) that is not finite or is below 0; -1: none
+static inline int tdk_first_bad_weight(const float* w, int n) {
+  for (int k = 0; k < n; k++)
+    if (!(isfinite(w[k]) && w[k] >= 0.0f)) return k;
+  return -1;
+}
+
+// true: a thread's four adjacent pixels can go as whole vectors of `bytes` bytes: rows hold whole groups of four and start on the
+// vector's alignment
+static inline bool tdk_vec4_ok(int width, const void* ptr, size_t bytes) { return width % 4 == 0 && tdk_aligned(ptr, bytes); }
+
+// The taps of a Gaussian of `sigma` in [lo, hi], cut at R = ceil(3 sigma) and normalised to w0 + 2 (w1 + .. + wR) = 1 in float64:
+// weights[0 .. max_radius] (zeros behind R) and *radius = R.  An entry point's hi keeps R <= max_radius <= TDK_TAPS_MAX_RADIUS.
+constexpr int TDK_TAPS_MAX_RADIUS = 12;
+static inline int tdk_gaussian_taps(const char* who, float sigma, float lo, float hi, int max_radius, float* weights, int* radius) {
+  TDK_REQUIRE(weights && radius, "%s: null pointer", who);
+  TDK_REQUIRE(sigma >= lo && sigma <= hi, "%s: sigma must lie in [%g, %g]", who, (double)lo, (double)hi);
+  const double s = (double)sigma;
+  const int R = (int)ceil(3.0 * s);
+  TDK_REQUIRE(R <= max_radius && max_radius <= TDK_TAPS_MAX_RADIUS, "%s: radius %d beyond the %d taps of the call", who, R, max_radius);
+  double w[TDK_TAPS_MAX_RADIUS + 1] = {1.0}, tail = 0.0;
+  for (int k = 1; k <= R; k++) {
+    w[k] = exp(-(double)(k * k) / (2.0 * s * s));
+    tail += w[k];
+  }
+  const double norm = w[0] + 2.0 * tail;
+  for (int k = 0; k <= max_radius; k++) weights[k] = k <= R ? (float)(w[k] / norm) : 0.0f;
+  *radius = R;
+  return TDK_OK;
+}
 
 // true: the byte ranges [p, p + pn) and [q, q + qn) share nothing
 static inline bool tdk_disjoint(const void* p, size_t pn, const void* q, size_t qn) {

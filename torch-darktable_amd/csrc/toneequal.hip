@@ -26,7 +26,6 @@
 namespace {
 
 constexpr int TE_THREADS = 256;
-constexpr int TE_MAX_SIZE = 65535;
 constexpr int TE_RMAX = TDK_TONEEQ_MAX_RADIUS;
 constexpr int TE_BAND = 16;                       // pixel rows of a wave of te_cells
 constexpr int TE_CT = 32;                         // te_coeff: a tile of TE_CT x TE_CT cells
@@ -47,8 +46,7 @@ struct TeArgs {
   float w0, w1, w2;
 };
 
-__device__ __forceinline__ float te_pos(float v) { return v > 0.0f ? v : 0.0f; }
-__device__ __forceinline__ float te_lum(const TeArgs& a, float r, float g, float b) { return te_pos((a.w0 * r + a.w1 * g) + a.w2 * b); }
+__device__ __forceinline__ float te_lum(const TeArgs& a, float r, float g, float b) { return tdk_pos((a.w0 * r + a.w1 * g) + a.w2 * b); }
 
 // TE_PX pixels of a row from column x0 on as v[3 * i + c]; columns past the row's end repeat its last pixel
 template <typename T> __device__ __forceinline__ void te_load(const T* __restrict__ row, int x0, int w, float* v);
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(TE_THREADS) void te_coeff(const float* __restrict__
       s2 = s2 + lds.h2[at + t * TE_CT];
     }
     const float mean = s1 * a.inv, corr = s2 * a.inv;
-    const float var = te_pos(corr - mean * mean);
+    const float var = tdk_pos(corr - mean * mean);
     const float ga = var / (var + a.eps);
     const size_t o = (size_t)cy * a.cw + cx;
     ca[o] = ga;
@@ -328,7 +326,6 @@ __global__ __launch_bounds__(TE_THREADS) void te_apply(const T* __restrict__ src
 }
 
 bool te_cell_ok(int cell) { return cell == 2 || cell == 4 || cell == 8 || cell == 16; }
-bool te_size_ok(int width, int height) { return width >= 1 && height >= 1 && width <= TE_MAX_SIZE && height <= TE_MAX_SIZE; }
 
 // Run a statement with the cell size S as a constant; the caller has checked `cell`.
 #define TE_DISPATCH_CELL(cell, S, ...)                       \
@@ -361,12 +358,12 @@ int te_launch(const void* src, void* dst, float* mask_out, float* planes, const 
 TDK_EXPORT int tdk_toneeq_abi_version(void) { return TDK_TONEEQ_ABI_VERSION; }
 
 TDK_EXPORT size_t tdk_toneeq_workspace_bytes(int width, int height, int cell) {
-  if (!te_size_ok(width, height) || !te_cell_ok(cell)) return 0;
+  if (!tdk_frame_size_ok(width, height) || !te_cell_ok(cell)) return 0;
   return (size_t)3 * tdk_div_up(width, cell) * tdk_div_up(height, cell) * sizeof(float) + TE_WS_ALIGN;
 }
 
 TDK_EXPORT size_t tdk_toneeq_lds_bytes(int dtype, int cell, int radius) {
-  if ((dtype != TDK_F32 && dtype != TDK_F16) || !te_cell_ok(cell) || radius < 0 || radius > TE_RMAX) return 0;
+  if (!tdk_float_dtype_ok(dtype) || !te_cell_ok(cell) || radius < 0 || radius > TE_RMAX) return 0;
   size_t apply = 0;
   TE_DISPATCH_CELL(cell, S, apply = te_apply_lds<S>());
   return apply > sizeof(TeCoeffLds) ? apply : sizeof(TeCoeffLds);
@@ -380,12 +377,13 @@ TDK_EXPORT int tdk_toneeq(const void* src, void* dst, float* mask_out, void* wor
   TDK_REQUIRE(workspace, "%s: null pointer (workspace)", who);
   TDK_REQUIRE(table, "%s: null pointer (table)", who);
   TDK_REQUIRE(weights, "%s: null pointer (weights)", who);
-  TDK_REQUIRE(te_size_ok(width, height), "%s: frame size %dx%d outside 1..%d", who, width, height, TE_MAX_SIZE);
-  TDK_REQUIRE(dtype == TDK_F32 || dtype == TDK_F16, "%s: unsupported dtype tag %d", who, dtype);
+  TDK_REQUIRE(tdk_frame_size_ok(width, height), "%s: frame size %dx%d outside 1..%d", who, width, height, TDK_FRAME_MAX_SIZE);
+  TDK_REQUIRE(tdk_float_dtype_ok(dtype), "%s: unsupported dtype tag %d", who, dtype);
   TDK_REQUIRE(te_cell_ok(cell), "%s: cell must be 2, 4, 8 or 16, got %d", who, cell);
   TDK_REQUIRE(radius >= 0 && radius <= TE_RMAX, "%s: radius must be 0..%d, got %d", who, TE_RMAX, radius);
   TDK_REQUIRE(eps > 0.0f && isfinite(eps), "%s: eps must be finite and > 0", who);
-  for (int k = 0; k < 3; k++) TDK_REQUIRE(isfinite(weights[k]) && weights[k] >= 0.0f, "%s: weights must be finite and >= 0 (weights[%d])", who, k);
+  const int bad_weight = tdk_first_bad_weight(weights, 3);
+  TDK_REQUIRE(bad_weight < 0, "%s: weights must be finite and >= 0 (weights[%d])", who, bad_weight);
   TDK_REQUIRE(flags == 0, "%s: flags is reserved and must be 0, got %d", who, flags);
   TDK_REQUIRE(tdk_aligned(table, 4), "%s: table must be aligned to 4 bytes", who);
   TDK_REQUIRE(tdk_aligned(mask_out, 4), "%s: mask_out must be aligned to 4 bytes", who);

@@ -28,6 +28,7 @@ import torch
 from ._frames import MAX_SIZE, require_cuda_device
 from ._native import (TDK_CA_BICUBIC, TDK_CA_BILINEAR, TDK_CA_LINEAR, TDK_CA_MAX_FRAMES, TDK_CA_MAX_SHIFT, TDK_CA_POLY3, TDK_CA_SUMS, TDK_CA_TILE_H, TDK_CA_TILE_W,
                       TDK_F16, TDK_F32, check, lib)
+from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .noiseprofile import NoiseModel
@@ -36,11 +37,6 @@ from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _INTERPS = {'bilinear': TDK_CA_BILINEAR, 'bicubic': TDK_CA_BICUBIC}
 _FITS = {'linear': TDK_CA_LINEAR, 'poly3': TDK_CA_POLY3}
-
-
-def _f32(value) -> float:
-    """The float32 nearest `value`, as a Python float."""
-    return ctypes.c_float(float(value)).value
 
 
 class ChromaticAberration:

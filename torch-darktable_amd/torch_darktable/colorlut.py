@@ -29,14 +29,10 @@ import torch
 
 from ._frames import TAGS, require_cuda_device
 from ._native import TDK_LUT_GLOBAL, TDK_LUT_MAX_SHAPER, TDK_LUT_MAX_SIZE, TDK_LUT_TETRAHEDRAL, TDK_LUT_TRILINEAR, check, lib
+from ._stage import as_float32 as _f32
 from .torch_darktable_extension import _ptr, _require, _stream
 
 _INTERPOLATIONS = {'tetrahedral': TDK_LUT_TETRAHEDRAL, 'trilinear': TDK_LUT_TRILINEAR}
-
-
-def _f32(value) -> float:
-    """The float32 nearest `value`, as a Python float."""
-    return ctypes.c_float(float(value)).value
 
 
 def _scale(entries: int, lo: float, hi: float, what: str) -> float:

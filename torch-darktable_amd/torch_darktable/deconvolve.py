@@ -20,23 +20,20 @@ the object, one set per stream.  No synchronisation: capturable in a HIP graph f
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
-from ._frames import TAGS, check_frame, check_size, require_cuda_device
-from ._native import (TDK_DECONV_FUSE_SHIFT, TDK_DECONV_MASK, TDK_DECONV_MAX_ITERATIONS, TDK_DECONV_MAX_RADIUS, TDK_DECONV_TILE, TDK_F16, TDK_F32, check,
-                      lib)
-from ._streams import StreamBuffers
+from ._frames import TAGS
+from ._native import TDK_DECONV_FUSE_SHIFT, TDK_DECONV_MASK, TDK_DECONV_MAX_ITERATIONS, TDK_DECONV_MAX_RADIUS, TDK_DECONV_TILE, check, lib
+from ._stage import FrameStage, SeparableTaps, as_float32, luma_weights
 from .torch_darktable_extension import _ptr, _stream
 
-REC709 = (0.2126, 0.7152, 0.0722)
 MAX_GAIN = 16.0
 BUILT_FUSED = {1: 6, 2: 4, 4: 2}   # F of an instantiation that was built: the largest radius it takes
 
 
-class Deconvolve:
+class Deconvolve(FrameStage):
     """Deconvolve (H, W, 1 or 3) frames of one size (width, height).  sigma: the Gaussian PSF; iterations: N, 0 returns the input;
     threshold: the contrast, in the square-root domain, below which nothing is sharpened (None: no mask); max_gain: the largest
     factor a pixel is scaled by, up or down; weights: the luminance weights of three-channel frames."""
@@ -45,14 +42,8 @@ class Deconvolve:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], sigma: float = 0.7, iterations: int = 8, threshold: float | None = 0.02,
                  max_gain: float = 4.0, weights=None):
-        sigma = ctypes.c_float(float(sigma)).value
-        if not 0.3 <= sigma <= 2.0:
-            raise ValueError(f'sigma must lie in [0.3, 2], got {sigma}')
-        buf, radius = (ctypes.c_float * (TDK_DECONV_MAX_RADIUS + 1))(), ctypes.c_int(0)
-        if lib.tdk_deconv_weights(sigma, buf, ctypes.byref(radius)) != 0:
-            raise ValueError(lib.tdk_last_error().decode('utf-8', 'replace'))
-        self._setup(device, image_size, tuple(buf[: radius.value + 1]), iterations, threshold, max_gain, weights)
-        self.sigma: float | None = sigma
+        taps = SeparableTaps.from_sigma(lib.tdk_deconv_weights, as_float32(sigma), 0.3, 2.0, TDK_DECONV_MAX_RADIUS)
+        self._setup(device, image_size, taps, iterations, threshold, max_gain, weights)
 
     @staticmethod
     def from_weights(device: torch.device, image_size: tuple[int, int], taps, iterations: int = 8, threshold: float | None = 0.02, max_gain: float = 4.0,
@@ -60,49 +51,35 @@ class Deconvolve:
         """A caller's own symmetric PSF: taps (w0, w1, .. wR), 1 <= R <= 6, finite and >= 0, used as float32.  They are taken as
         they are; a PSF that keeps a flat area flat needs w0 + 2 (w1 + .. + wR) = 1."""
         self = Deconvolve.__new__(Deconvolve)
-        self._setup(device, image_size, tuple(ctypes.c_float(float(w)).value for w in taps), iterations, threshold, max_gain, weights)
-        self.sigma = None
+        self._setup(device, image_size, taps, iterations, threshold, max_gain, weights)
         return self
 
     def _setup(self, device, image_size, taps, iterations, threshold, max_gain, weights) -> None:
-        require_cuda_device(device)
-        check_size('Image', image_size)
-        if not 2 <= len(taps) <= TDK_DECONV_MAX_RADIUS + 1:
-            raise ValueError(f'taps must hold 2..{TDK_DECONV_MAX_RADIUS + 1} values (radius 1..{TDK_DECONV_MAX_RADIUS}), got {len(taps)}')
-        if not all(math.isfinite(w) and w >= 0.0 for w in taps):
-            raise ValueError(f'taps must be finite and >= 0, got {taps}')
+        super().__init__(device, image_size)
+        self._taps = SeparableTaps.from_values(taps, TDK_DECONV_MAX_RADIUS, 'taps')
+        self.sigma: float | None = self._taps.sigma
         if int(iterations) != iterations or not 0 <= int(iterations) <= TDK_DECONV_MAX_ITERATIONS:
             raise ValueError(f'iterations must be an integer in 0..{TDK_DECONV_MAX_ITERATIONS}, got {iterations}')
         if threshold is not None:
-            threshold = ctypes.c_float(float(threshold)).value
+            threshold = as_float32(threshold)
             if not (math.isfinite(threshold) and threshold > 0.0):
                 raise ValueError(f'threshold must be None or finite and > 0 as a float32, got {threshold}')
-        max_gain = ctypes.c_float(float(max_gain)).value
+        max_gain = as_float32(max_gain)
         if not 1.0 <= max_gain <= MAX_GAIN:
             raise ValueError(f'max_gain must lie in [1, {MAX_GAIN:g}], got {max_gain}')
-        weights = REC709 if weights is None else tuple(float(v) for v in weights)
-        if len(weights) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in weights):
-            raise ValueError(f'weights must be three finite values >= 0, got {weights}')
-        self._device = device
-        self.width, self.height = int(image_size[0]), int(image_size[1])
-        self._taps = taps
-        self._c_taps = (ctypes.c_float * len(taps))(*taps)
+        self.weights, self._c_weights = luma_weights(weights)
         self.iterations, self.threshold, self.max_gain = int(iterations), threshold, max_gain
-        self.weights = tuple(ctypes.c_float(v).value for v in weights)
-        self._c_weights = (ctypes.c_float * 3)(*self.weights)
         self._forced = 0   # F forced through the flags (tests and measurements); 0: the library's choice
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            self._workspace(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
+        self._prepare()
 
     @property
     def taps(self) -> tuple[float, ...]:
         """The PSF's taps w0 .. wR as float32 values."""
-        return self._taps
+        return self._taps.values
 
     @property
     def radius(self) -> int:
-        return len(self._taps) - 1
+        return self._taps.radius
 
     @property
     def fused_iterations(self) -> int:
@@ -121,17 +98,12 @@ class Deconvolve:
     def launches(self) -> int:
         return 1 if self.iterations == 0 else -(-self.iterations // self.fused_iterations)
 
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
-
     def _flags(self) -> int:
         return (TDK_DECONV_MASK if self.threshold is not None else 0) | (self._forced << TDK_DECONV_FUSE_SHIFT)
 
     def __repr__(self):
-        psf = f'sigma={self.sigma:g}' if self.sigma is not None else f'taps={self._taps}'
         threshold = None if self.threshold is None else f'{self.threshold:g}'
-        return f'Deconvolve({self.width}x{self.height}, {psf}, radius={self.radius}, iterations={self.iterations}, threshold={threshold}, max_gain={self.max_gain:g})'
+        return f'Deconvolve({self.width}x{self.height}, {self._taps!r}, radius={self.radius}, iterations={self.iterations}, threshold={threshold}, max_gain={self.max_gain:g})'
 
     def workspace_bytes(self) -> int:
         """Bytes of the planes u travels in between the launches; 0 when the call is one launch.  With a forced F: what any F needs."""
@@ -143,21 +115,13 @@ class Deconvolve:
         """LDS one workgroup takes on frames of this kind (0: not a legal call)."""
         return int(lib.tdk_deconv_lds_bytes(channels, TAGS.get(dtype, -1), self.radius, self._flags()))
 
-    def _workspace(self, device: torch.device) -> torch.Tensor:
-        """The planes between the launches, one buffer per stream: the object may be used from several streams at once.  The buffer
-        of the stream current at construction exists from then on, so a capture allocates nothing.  Every value read was written by
-        the same call: the buffer is never cleared."""
-        return self._workspaces.get(self.workspace_bytes(), device)
-
     def _run(self, image: torch.Tensor, want_mask: bool):
-        height, width, channels, tag = check_frame(image, (self.height, self.width), 'Deconvolve')
-        if tag not in (TDK_F32, TDK_F16):
-            raise ValueError(f'image must be float32 or float16, got {image.dtype}')
+        height, width, channels, tag = self._float_frame(image, 'Deconvolve')
         with torch.cuda.device(image.device):
             out = torch.empty_like(image)
             m = torch.empty((height, width), dtype=torch.float32, device=image.device) if want_mask else None
             ws = self._workspace(image.device)
-            rc = lib.tdk_deconv(_ptr(image), _ptr(out), _ptr(m), _ptr(ws if ws.numel() else None), width, height, channels, tag, self._c_taps, self.radius,
+            rc = lib.tdk_deconv(_ptr(image), _ptr(out), _ptr(m), _ptr(ws if ws.numel() else None), width, height, channels, tag, self._taps.c_array, self.radius,
                                 self.iterations, 1.0 if self.threshold is None else self.threshold, self.max_gain, self._c_weights, self._flags(), _stream())
         check(rc)
         return out, m

@@ -22,15 +22,14 @@ synchronisation: capturable in a HIP graph from the first call, and bit-reproduc
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
-from ._frames import TAGS, check_frame, check_size, require_cuda_device
+from ._frames import TAGS
 from ._native import (TDK_DEFRINGE_GROUPS_SHIFT, TDK_DEFRINGE_LINEAR, TDK_DEFRINGE_MAX_GROUPS, TDK_DEFRINGE_MAX_RADIUS, TDK_DEFRINGE_MAX_SAMPLE_RADIUS,
-                      TDK_DEFRINGE_STATIC, TDK_DEFRINGE_TILE, TDK_F16, TDK_F32, check, lib)
-from ._streams import StreamBuffers
+                      TDK_DEFRINGE_STATIC, TDK_DEFRINGE_TILE, check, lib)
+from ._stage import FrameStage, SeparableTaps, as_float32
 from .torch_darktable_extension import _ptr, _stream
 
 MODES = ('global', 'static')
@@ -38,24 +37,19 @@ DOMAINS = ('sqrt', 'linear')
 STATS_BYTES = 16   # tdk_defringe_stats: S as 64 bits, th as float32, a reserved word
 
 
-class Defringe:
+class Defringe(FrameStage):
     """Defringe (H, W, 3) frames of one size (width, height).  sigma: the Gaussian that defines "the chroma around a pixel"; radius:
     S_r, the disc a fringed pixel's new chroma is averaged over; strength: the threshold in units of the frame's average edge chroma
     (mode 'global') or the threshold itself (mode 'static'); floor: the least threshold; domain: the values the stage works on,
     square roots of the samples or the samples."""
 
     TILE = (TDK_DEFRINGE_TILE, TDK_DEFRINGE_TILE)  # (width, height) of one workgroup's output tile (csrc/defringe.hip: DF_T)
+    _record_bytes = STATS_BYTES
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], sigma: float = 2.0, radius: int = 6, strength: float = 2.5, floor: float = 1e-4,
                  mode: str = 'global', domain: str = 'sqrt'):
-        sigma = ctypes.c_float(float(sigma)).value
-        if not 0.5 <= sigma <= 4.0:
-            raise ValueError(f'sigma must lie in [0.5, 4], got {sigma}')
-        buf, blur_radius = (ctypes.c_float * (TDK_DEFRINGE_MAX_RADIUS + 1))(), ctypes.c_int(0)
-        if lib.tdk_defringe_weights(sigma, buf, ctypes.byref(blur_radius)) != 0:
-            raise ValueError(lib.tdk_last_error().decode('utf-8', 'replace'))
-        self._setup(device, image_size, tuple(buf[: blur_radius.value + 1]), radius, strength, floor, mode, domain)
-        self.sigma: float | None = sigma
+        taps = SeparableTaps.from_sigma(lib.tdk_defringe_weights, as_float32(sigma), 0.5, 4.0, TDK_DEFRINGE_MAX_RADIUS)
+        self._setup(device, image_size, taps, radius, strength, floor, mode, domain)
 
     @staticmethod
     def from_weights(device: torch.device, image_size: tuple[int, int], taps, radius: int = 6, strength: float = 2.5, floor: float = 1e-4, mode: str = 'global',
@@ -63,56 +57,42 @@ class Defringe:
         """A caller's own symmetric blur: taps (w0, w1, .. wR), 1 <= R <= 12, finite and >= 0, used as float32.  They are taken as
         they are; a blur that keeps a flat area flat needs w0 + 2 (w1 + .. + wR) = 1."""
         self = Defringe.__new__(Defringe)
-        self._setup(device, image_size, tuple(ctypes.c_float(float(w)).value for w in taps), radius, strength, floor, mode, domain)
-        self.sigma = None
+        self._setup(device, image_size, taps, radius, strength, floor, mode, domain)
         return self
 
     def _setup(self, device, image_size, taps, radius, strength, floor, mode, domain) -> None:
-        require_cuda_device(device)
-        check_size('Image', image_size)
-        if not 2 <= len(taps) <= TDK_DEFRINGE_MAX_RADIUS + 1:
-            raise ValueError(f'taps must hold 2..{TDK_DEFRINGE_MAX_RADIUS + 1} values (radius 1..{TDK_DEFRINGE_MAX_RADIUS}), got {len(taps)}')
-        if not all(math.isfinite(w) and w >= 0.0 for w in taps):
-            raise ValueError(f'taps must be finite and >= 0, got {taps}')
+        super().__init__(device, image_size)
+        self._taps = SeparableTaps.from_values(taps, TDK_DEFRINGE_MAX_RADIUS, 'taps')
+        self.sigma: float | None = self._taps.sigma
         if int(radius) != radius or not 1 <= int(radius) <= TDK_DEFRINGE_MAX_SAMPLE_RADIUS:
             raise ValueError(f'radius must be an integer in 1..{TDK_DEFRINGE_MAX_SAMPLE_RADIUS}, got {radius}')
-        strength = ctypes.c_float(float(strength)).value
+        strength = as_float32(strength)
         if not (math.isfinite(strength) and strength >= 0.0):
             raise ValueError(f'strength must be finite and >= 0 as a float32, got {strength}')
-        floor = ctypes.c_float(float(floor)).value
+        floor = as_float32(floor)
         if not (math.isfinite(floor) and floor > 0.0):
             raise ValueError(f'floor must be finite and > 0 as a float32, got {floor}')
         if mode not in MODES:
             raise ValueError(f'mode must be one of {MODES}, got {mode!r}')
         if domain not in DOMAINS:
             raise ValueError(f'domain must be one of {DOMAINS}, got {domain!r}')
-        self._device = device
-        self.width, self.height = int(image_size[0]), int(image_size[1])
-        self._taps = taps
-        self._c_taps = (ctypes.c_float * len(taps))(*taps)
         self.radius, self.strength, self.floor, self.mode, self.domain = int(radius), strength, floor, mode, domain
         self._groups = 0   # a cap on the workgroups that gather the statistic (tests and measurements); 0: the library's
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            self._buffers(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
+        self._prepare()
 
     @property
     def taps(self) -> tuple[float, ...]:
         """The blur's taps w0 .. wR as float32 values."""
-        return self._taps
+        return self._taps.values
 
     @property
     def blur_radius(self) -> int:
         """R"""
-        return len(self._taps) - 1
+        return self._taps.radius
 
     @property
     def launches(self) -> int:
         return 2
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
 
     @property
     def max_groups(self) -> int:
@@ -132,8 +112,7 @@ class Defringe:
                 | (self._groups << TDK_DEFRINGE_GROUPS_SHIFT))
 
     def __repr__(self):
-        blur = f'sigma={self.sigma:g}' if self.sigma is not None else f'taps={self._taps}'
-        return (f'Defringe({self.width}x{self.height}, {blur}, blur_radius={self.blur_radius}, radius={self.radius}, strength={self.strength:g}, '
+        return (f'Defringe({self.width}x{self.height}, {self._taps!r}, blur_radius={self.blur_radius}, radius={self.radius}, strength={self.strength:g}, '
                 f'floor={self.floor:g}, mode={self.mode!r}, domain={self.domain!r})')
 
     def workspace_bytes(self) -> int:
@@ -145,24 +124,18 @@ class Defringe:
         return int(lib.tdk_defringe_lds_bytes(TAGS.get(dtype, -1), self.blur_radius, self.radius, self._flags()))
 
     def _buffers(self, device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
-        """(the record of S and th, the workspace), one buffer per stream: the object may be used from several streams at once.  The
-        buffer of the stream current at construction exists from then on, so a capture allocates nothing.  Every value read was
-        written by the same call: the buffer is never cleared."""
-        buf = self._workspaces.get(STATS_BYTES + self.workspace_bytes(), device)
+        """(the record of S and th, the workspace): the two parts of the stream's buffer."""
+        buf = self._workspace(device)
         return buf[:STATS_BYTES], buf[STATS_BYTES:]
 
     def _run(self, image: torch.Tensor, want_mask: bool, want_edge: bool):
-        height, width, channels, tag = check_frame(image, (self.height, self.width), 'Defringe')
-        if channels != 3:
-            raise ValueError(f'image must have 3 channels, got {channels}')
-        if tag not in (TDK_F32, TDK_F16):
-            raise ValueError(f'image must be float32 or float16, got {image.dtype}')
+        height, width, _, tag = self._float_frame(image, 'Defringe', 'image must have 3 channels')
         with torch.cuda.device(image.device):
             out = torch.empty_like(image)
             m = torch.empty((height, width), dtype=torch.uint8, device=image.device) if want_mask else None
             e = torch.empty((height, width), dtype=torch.float32, device=image.device) if want_edge else None
             stats, ws = self._buffers(image.device)
-            rc = lib.tdk_defringe(_ptr(image), _ptr(out), _ptr(m), _ptr(e), _ptr(stats), _ptr(ws), width, height, tag, self._c_taps, self.blur_radius, self.radius,
+            rc = lib.tdk_defringe(_ptr(image), _ptr(out), _ptr(m), _ptr(e), _ptr(stats), _ptr(ws), width, height, tag, self._taps.c_array, self.blur_radius, self.radius,
                                   self.strength, self.floor, self._flags(), _stream())
         check(rc)
         return out, m, e
@@ -180,8 +153,7 @@ class Defringe:
     def threshold(self) -> tuple[torch.Tensor, torch.Tensor]:
         """(S, th) of the last call on the current stream: views of the device record, an int64 and a float32 scalar, valid in stream
         order and overwritten by the next call on this stream.  No synchronisation."""
-        device = torch.device('cuda', torch.cuda.current_device()) if self._device.index is None else self._device
-        stats, _ = self._buffers(device)
+        stats, _ = self._buffers(self._home_device())
         return stats[:8].view(torch.int64)[0], stats[8:12].view(torch.float32)[0]
 
 

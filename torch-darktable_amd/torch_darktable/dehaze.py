@@ -25,22 +25,20 @@ object, one per stream: capturable in a HIP graph from the first call, and bit-r
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
-from ._frames import TAGS, check_frame, check_size, require_cuda_device
-from ._native import TDK_DEHAZE_MAX_CELLS, TDK_DEHAZE_MAX_DARK_RADIUS, TDK_DEHAZE_MAX_RADIUS, TDK_F16, TDK_F32, check, lib
-from ._streams import StreamBuffers
+from ._frames import TAGS
+from ._native import TDK_DEHAZE_MAX_CELLS, TDK_DEHAZE_MAX_DARK_RADIUS, TDK_DEHAZE_MAX_RADIUS, check, lib
+from ._stage import FrameStage, as_float32, luma_weights
 from .torch_darktable_extension import _ptr, _stream
 
-REC709 = (0.2126, 0.7152, 0.0722)
 CELLS = (2, 4, 8, 16)
 MIN_FLOOR = 2.0 ** -6
 
 
-class Dehaze:
+class Dehaze(FrameStage):
     """Remove haze from (H, W, 3) frames of one size (width, height).  strength: how much of the estimated haze goes (1: all of it,
     which looks flat; 0: none); floor: the least transmission divided by; dark_radius, radius: the windows of the dark channel and of
     the guided filter, in cells; quantile: the share of cells, the haziest, whose mean is the ambient light."""
@@ -49,49 +47,37 @@ class Dehaze:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], strength: float = 0.9, floor: float = 0.1, cell: int = 8, dark_radius: int = 1,
                  radius: int = 4, eps: float = 1e-3, quantile: float = 0.01, weights=None):
-        require_cuda_device(device)
-        check_size('Image', image_size)
+        super().__init__(device, image_size)
         if cell not in CELLS:
             raise ValueError(f'cell must be one of {CELLS}, got {cell}')
-        width, height = int(image_size[0]), int(image_size[1])
-        cells = -(-width // cell) * -(-height // cell)
+        cells = -(-self.width // cell) * -(-self.height // cell)
         if cells > TDK_DEHAZE_MAX_CELLS:
             raise ValueError(f'the grid of {cells} cells is larger than {TDK_DEHAZE_MAX_CELLS}: use a larger cell')
         if int(dark_radius) != dark_radius or not 0 <= int(dark_radius) <= TDK_DEHAZE_MAX_DARK_RADIUS:
             raise ValueError(f'dark_radius must be an integer in 0..{TDK_DEHAZE_MAX_DARK_RADIUS}, got {dark_radius}')
         if int(radius) != radius or not 0 <= int(radius) <= TDK_DEHAZE_MAX_RADIUS:
             raise ValueError(f'radius must be an integer in 0..{TDK_DEHAZE_MAX_RADIUS}, got {radius}')
-        eps = ctypes.c_float(float(eps)).value
+        eps = as_float32(eps)
         if not (math.isfinite(eps) and eps > 0.0):
             raise ValueError(f'eps must be finite and > 0 as a float32, got {eps}')
-        strength = ctypes.c_float(float(strength)).value
+        strength = as_float32(strength)
         if not 0.0 <= strength <= 1.0:
             raise ValueError(f'strength must be in 0..1, got {strength}')
-        floor = ctypes.c_float(float(floor)).value
+        floor = as_float32(floor)
         if not MIN_FLOOR <= floor <= 1.0:
             raise ValueError(f'floor must be in 2^-6..1, got {floor}')
         quantile = float(quantile)
         if not 0.0 < quantile <= 1.0:
             raise ValueError(f'quantile must be in (0, 1], got {quantile}')
-        weights = REC709 if weights is None else tuple(float(v) for v in weights)
-        if len(weights) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in weights):
-            raise ValueError(f'weights must be three finite values >= 0, got {weights}')
-        self._device = device
-        self.width, self.height = width, height
+        self.weights, self._c_weights = luma_weights(weights)
         self.cell, self.dark_radius, self.radius = int(cell), int(dark_radius), int(radius)
         self.eps, self.strength, self.floor, self.quantile = eps, strength, floor, quantile
         self.cells = cells
         self.count = max(1, math.floor(quantile * cells))   # K: the cells whose mean is the ambient light, before ties
-        self.weights = tuple(ctypes.c_float(v).value for v in weights)
-        self._c_weights = (ctypes.c_float * 3)(*self.weights)
         self._fixed = False                       # True: set_ambient gave the ambient light, calls do not estimate
         self._host_ambient = torch.zeros(4, dtype=torch.float32)   # kept by the object: set_ambient copies from it in stream order
-        self._ambient: torch.Tensor | None = None
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            where = torch.device('cuda', torch.cuda.current_device()) if device.index is None else device
-            self._ambient = torch.zeros(4, dtype=torch.float32, device=where)
-            self._workspace(where)
+        where = self._prepare()
+        self._ambient: torch.Tensor | None = None if where is None else torch.zeros(4, dtype=torch.float32, device=where)
 
     @property
     def ambient(self) -> torch.Tensor | None:
@@ -102,10 +88,6 @@ class Dehaze:
     @property
     def ambient_is_fixed(self) -> bool:
         return self._fixed
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
 
     def __repr__(self):
         return (f'Dehaze({self.width}x{self.height}, strength={self.strength:g}, floor={self.floor:g}, cell={self.cell}, dark_radius={self.dark_radius}, '
@@ -139,18 +121,8 @@ class Dehaze:
             self._ambient[:source.numel()].copy_(source, non_blocking=True)
         self._fixed = True
 
-    def _workspace(self, device: torch.device) -> torch.Tensor:
-        """The cell planes between the launches, one buffer per stream: the object may be used from several streams at once.  The
-        buffer of the stream current at construction exists from then on, so a capture allocates nothing.  Every value read was
-        written by the same call: the buffer is never cleared."""
-        return self._workspaces.get(self.workspace_bytes(), device)
-
     def _check(self, image: torch.Tensor, ambient):
-        height, width, channels, tag = check_frame(image, (self.height, self.width), 'Dehaze')
-        if channels != 3:
-            raise ValueError(f'image channels must be 3, got {channels}')
-        if tag not in (TDK_F32, TDK_F16):
-            raise ValueError(f'image must be float32 or float16, got {image.dtype}')
+        height, width, _, tag = self._float_frame(image, 'Dehaze', 'image channels must be 3')
         if self._ambient is None or self._ambient.device != image.device:
             raise RuntimeError(f'Dehaze was built for {None if self._ambient is None else self._ambient.device}, the image is on {image.device}')
         if ambient is not None:

@@ -26,7 +26,6 @@ so a captured call follows `set_exposure` and `set_curve`.
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -34,9 +33,9 @@ import torch
 from ._frames import TAGS, require_cuda_device
 from ._native import (TDK_F16, TDK_F32, TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE, TDK_FILMIC_EV_MIN, TDK_FILMIC_LUMA, TDK_FILMIC_MAX, TDK_FILMIC_NONE,
                       TDK_FILMIC_POWER, TDK_FILMIC_STEPS, TDK_FILMIC_TABLE, check, lib)
+from ._stage import as_float32, home_device, luma_weights
 from .torch_darktable_extension import _ptr, _require, _stream
 
-REC709 = (0.2126, 0.7152, 0.0722)
 NORMS = {'max': TDK_FILMIC_MAX, 'luma': TDK_FILMIC_LUMA, 'power': TDK_FILMIC_POWER, 'none': TDK_FILMIC_NONE}
 _SPLINE = ('grey', 'black_ev', 'white_ev', 'contrast', 'latitude', 'target', 'output_power', 'desaturate')
 
@@ -222,14 +221,10 @@ class Filmic:
         require_cuda_device(device)
         if norm not in NORMS:
             raise ValueError(f'norm must be one of {tuple(NORMS)}, got {norm!r}')
-        weights = REC709 if weights is None else tuple(float(v) for v in weights)
-        if len(weights) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in weights):
-            raise ValueError(f'weights must be three finite values >= 0, got {weights}')
+        self.weights, self._c_weights = luma_weights(weights)
         oetf = encoding_curve(encoding)
         self._device = device
         self.norm, self.encoding = norm, encoding
-        self.weights = tuple(ctypes.c_float(v).value for v in weights)
-        self._c_weights = (ctypes.c_float * 3)(*self.weights)
         self.host_encode = None if oetf is None else _table(oetf(self.encoding_nodes()), TDK_FILMIC_ENC_TABLE, 'encoding')
         self.host_curve: torch.Tensor | None = None     # (2, TDK_FILMIC_TABLE) float32: T, D
         self._host_exposure = 1.0
@@ -237,7 +232,7 @@ class Filmic:
         self._encode: torch.Tensor | None = None
         self._exposure: torch.Tensor | None = None
         if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            where = torch.device('cuda', torch.cuda.current_device()) if device.index is None else device
+            where = home_device(device)
             self._curve = torch.zeros((2, TDK_FILMIC_TABLE), dtype=torch.float32, device=where)
             self._exposure = torch.ones(1, dtype=torch.float32, device=where)
             self._encode = None if self.host_encode is None else self.host_encode.to(where)
@@ -291,7 +286,7 @@ class Filmic:
                 _require(value.device == self._exposure.device, f'exposure is on {value.device}, Filmic on {self._exposure.device}')
                 self._exposure.copy_(value.reshape(1), non_blocking=True)
             return
-        value = ctypes.c_float(_finite(value, 'exposure')).value
+        value = as_float32(_finite(value, 'exposure'))
         if not (math.isfinite(value) and value >= 0.0):
             raise ValueError(f'exposure must be finite and >= 0 as a float32, got {value}')
         self._host_exposure = value

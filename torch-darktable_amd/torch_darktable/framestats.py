@@ -28,17 +28,13 @@ import torch
 from ._frames import MAX_SIZE, require_cuda_device
 from ._native import (TDK_F16, TDK_F32, TDK_STATS_CHUNK, TDK_STATS_GRID, TDK_STATS_MAX_BINS, TDK_STATS_MAX_FRAMES, TDK_STATS_MAX_QUANTILES, TDK_U8, TDK_U16,
                       check, lib)
+from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
 _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint8: TDK_U8, torch.uint16: TDK_U16}
 _COUNTERS = 5  # below, above, nan, valid, sum
-
-
-def _f32(value) -> float:
-    """The float32 nearest `value`, as a Python float."""
-    return ctypes.c_float(float(value)).value
 
 
 @dataclass

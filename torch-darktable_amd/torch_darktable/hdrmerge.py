@@ -27,17 +27,13 @@ import torch
 
 from ._frames import MAX_SIZE, require_cuda_device
 from ._native import TDK_F16, TDK_F32, TDK_HDR_MAX_FRAMES, TDK_HDR_TILE_H, TDK_HDR_TILE_W, check, lib
+from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .noiseprofile import NoiseModel
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
 _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
-
-
-def _f32(value) -> float:
-    """The float32 nearest `value`, as a Python float."""
-    return ctypes.c_float(float(value)).value
 
 
 class HdrMerge:

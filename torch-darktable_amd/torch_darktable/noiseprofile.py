@@ -36,6 +36,7 @@ import torch
 from ._frames import MAX_SIZE, require_cuda_device
 from ._native import (TDK_F16, TDK_F32, TDK_NOISE_ALGEBRAIC, TDK_NOISE_GRID, TDK_NOISE_LEVELS, TDK_NOISE_MAX_BINS, TDK_NOISE_MAX_FRAMES, TDK_NOISE_STRIP_BYTES,
                       TDK_NOISE_UNBIASED, TDK_U16, check, lib)
+from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
@@ -44,11 +45,6 @@ _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint16: TDK_U16}
 _VST_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _INVERSES = {'algebraic': TDK_NOISE_ALGEBRAIC, 'unbiased': TDK_NOISE_UNBIASED}
 _COUNTERS = 9  # all, nan, clipped per colour
-
-
-def _f32(value) -> float:
-    """The float32 nearest `value`, as a Python float."""
-    return ctypes.c_float(float(value)).value
 
 
 @dataclass

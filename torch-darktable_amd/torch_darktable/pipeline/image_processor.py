@@ -55,6 +55,27 @@ class ImageSizeMismatchError(Exception):
         self.compressed_status: dict[str, torch.Tensor] = {}   # the raw codec's status per frame of the last process_*_compressed call
 
 
+def _stage_property(attr: str, name: str, cls: type, article: str, doc: str, sized: bool = True, also=None) -> property:
+    """The property `name` of an ImageProcessor that keeps an optional stage of type `cls` in `attr`.  The setter takes None or a
+    `cls`, built for the processor's image size when `sized`, that passes also(processor, stage) when given."""
+    def setter(self, stage) -> None:
+        if stage is not None:
+            if not isinstance(stage, cls):
+                raise TypeError(f'{name} must be {article} {cls.__name__} or None, got {type(stage).__name__}')
+            if sized and stage.image_size != tuple(self.image_size):
+                raise ValueError(f'{name} is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
+            if also is not None:
+                also(self, stage)
+        setattr(self, attr, stage)
+
+    return property(lambda self: getattr(self, attr), setter, doc=doc)
+
+
+def _same_pattern(processor, stage: LMMSE) -> None:
+    if stage.bayer_pattern != processor.bayer_pattern:
+        raise ValueError(f'demosaic is for {stage.bayer_pattern.name}, the processor for {processor.bayer_pattern.name}')
+
+
 class ImageProcessor:
     # haze removal on every demosaiced frame, behind `color` and in front of the tone equalizer: the property `dehaze` (every
     # constructor slot is pinned by the test of an earlier stage).  A class-level default, so that an object made without the
@@ -240,94 +261,19 @@ class ImageProcessor:
     def final_size(self) -> tuple[int, int]:
         return resize_longest_edge(self.image_size, self.settings.resize_width)
 
-    @property
-    def dehaze(self) -> Dehaze | None:
-        """The haze removal run on every demosaiced frame behind `color` and in front of `tone_equalizer`, so that bounds and metrics see
-        its result; None: no such stage."""
-        return self._dehaze
-
-    @dehaze.setter
-    def dehaze(self, stage: Dehaze | None) -> None:
-        if stage is not None:
-            if not isinstance(stage, Dehaze):
-                raise TypeError(f'dehaze must be a Dehaze or None, got {type(stage).__name__}')
-            if stage.image_size != tuple(self.image_size):
-                raise ValueError(f'dehaze is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
-        self._dehaze = stage
-
-    @property
-    def demosaic(self) -> LMMSE | None:
-        """The demosaic that takes the place of the method `settings.debayer` names, still followed by PostProcess when
+    dehaze = _stage_property('_dehaze', 'dehaze', Dehaze, 'a', """The haze removal run on every demosaiced frame behind `color` and in front of `tone_equalizer`, so that bounds and metrics see
+        its result; None: no such stage.""")
+    demosaic = _stage_property('_lmmse', 'demosaic', LMMSE, 'an', """The demosaic that takes the place of the method `settings.debayer` names, still followed by PostProcess when
         `settings.postprocess` is set; load_image then takes the unfused path (decode, white balance, demosaic), and with binary16
-        storage the stage writes binary16 itself.  None: bilinear, PPG or RCD, as `settings.debayer` says."""
-        return self._lmmse
-
-    @demosaic.setter
-    def demosaic(self, stage: LMMSE | None) -> None:
-        if stage is not None:
-            if not isinstance(stage, LMMSE):
-                raise TypeError(f'demosaic must be an LMMSE or None, got {type(stage).__name__}')
-            if stage.image_size != tuple(self.image_size):
-                raise ValueError(f'demosaic is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
-            if stage.bayer_pattern != self.bayer_pattern:
-                raise ValueError(f'demosaic is for {stage.bayer_pattern.name}, the processor for {self.bayer_pattern.name}')
-        self._lmmse = stage
-
-    @property
-    def defringe(self) -> Defringe | None:
-        """The purple-fringe removal run on every demosaiced frame behind `chroma_denoise` and in front of `capture_sharpen`: noise
-        does not set its threshold, and the deconvolution does not sharpen the halo; None: no such stage."""
-        return self._defringe
-
-    @defringe.setter
-    def defringe(self, stage: Defringe | None) -> None:
-        if stage is not None:
-            if not isinstance(stage, Defringe):
-                raise TypeError(f'defringe must be a Defringe or None, got {type(stage).__name__}')
-            if stage.image_size != tuple(self.image_size):
-                raise ValueError(f'defringe is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
-        self._defringe = stage
-
-    @property
-    def capture_sharpen(self) -> Deconvolve | None:
-        """The deconvolution run on every demosaiced frame behind `chroma_denoise` and in front of `color`: on linear camera RGB, after
-        the noise has been dealt with, so that every later stage sees its detail; None: no such stage."""
-        return self._capture_sharpen
-
-    @capture_sharpen.setter
-    def capture_sharpen(self, stage: Deconvolve | None) -> None:
-        if stage is not None:
-            if not isinstance(stage, Deconvolve):
-                raise TypeError(f'capture_sharpen must be a Deconvolve or None, got {type(stage).__name__}')
-            if stage.image_size != tuple(self.image_size):
-                raise ValueError(f'capture_sharpen is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
-        self._capture_sharpen = stage
-
-    @property
-    def filmic(self) -> Filmic | None:
-        """The scene-referred tone mapping that takes the place of `tonemap` on every frame (uint8 out); bounds, metrics and their moving
-        averages are computed as without it.  None: the mapper of the settings."""
-        return self._filmic
-
-    @filmic.setter
-    def filmic(self, stage: Filmic | None) -> None:
-        if stage is not None and not isinstance(stage, Filmic):
-            raise TypeError(f'filmic must be a Filmic or None, got {type(stage).__name__}')
-        self._filmic = stage
-
-    @property
-    def tone_equalizer(self) -> ToneEqualizer | None:
-        """The tone equalizer run on every demosaiced frame behind `color`, so that bounds and metrics see its result; None: no such stage."""
-        return self._tone_equalizer
-
-    @tone_equalizer.setter
-    def tone_equalizer(self, stage: ToneEqualizer | None) -> None:
-        if stage is not None:
-            if not isinstance(stage, ToneEqualizer):
-                raise TypeError(f'tone_equalizer must be a ToneEqualizer or None, got {type(stage).__name__}')
-            if stage.image_size != tuple(self.image_size):
-                raise ValueError(f'tone_equalizer is for {stage.width}x{stage.height}, the processor for {self.image_size[0]}x{self.image_size[1]}')
-        self._tone_equalizer = stage
+        storage the stage writes binary16 itself.  None: bilinear, PPG or RCD, as `settings.debayer` says.""", also=_same_pattern)
+    defringe = _stage_property('_defringe', 'defringe', Defringe, 'a', """The purple-fringe removal run on every demosaiced frame behind `chroma_denoise` and in front of `capture_sharpen`: noise
+        does not set its threshold, and the deconvolution does not sharpen the halo; None: no such stage.""")
+    capture_sharpen = _stage_property('_capture_sharpen', 'capture_sharpen', Deconvolve, 'a', """The deconvolution run on every demosaiced frame behind `chroma_denoise` and in front of `color`: on linear camera RGB, after
+        the noise has been dealt with, so that every later stage sees its detail; None: no such stage.""")
+    filmic = _stage_property('_filmic', 'filmic', Filmic, 'a', """The scene-referred tone mapping that takes the place of `tonemap` on every frame (uint8 out); bounds, metrics and their moving
+        averages are computed as without it.  None: the mapper of the settings.""", sized=False)
+    tone_equalizer = _stage_property('_tone_equalizer', 'tone_equalizer', ToneEqualizer, 'a',
+                                     """The tone equalizer run on every demosaiced frame behind `color`, so that bounds and metrics see its result; None: no such stage.""")
 
     @property
     def expected_bytes(self) -> int:

@@ -12,13 +12,13 @@ PyTorch's current stream, no workspace, no synchronisation: capturable in a HIP 
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
 from ._frames import TAGS, check_frame, require_cuda_device
 from ._native import TDK_SHARPEN_LIMIT, TDK_SHARPEN_LUMA, TDK_SHARPEN_MAX_RADIUS, check, lib
+from ._stage import SeparableTaps
 from .torch_darktable_extension import _ptr, _stream
 
 MAX_AMOUNT = 16.0
@@ -32,14 +32,7 @@ class Sharpen:
 
     def __init__(self, device: torch.device, sigma: float = 1.0, amount: float = 0.5, threshold: float = 0.0, luma: bool = True,
                  overshoot: float | None = None):
-        sigma = float(sigma)
-        if not 0.25 <= sigma <= 4.0:
-            raise ValueError(f'sigma must lie in [0.25, 4], got {sigma}')
-        buf, radius = (ctypes.c_float * (TDK_SHARPEN_MAX_RADIUS + 1))(), ctypes.c_int(0)
-        if lib.tdk_sharpen_weights(sigma, buf, ctypes.byref(radius)) != 0:
-            raise ValueError(lib.tdk_last_error().decode('utf-8', 'replace'))
-        self._setup(device, tuple(buf[: radius.value + 1]), amount, threshold, luma, overshoot)
-        self.sigma: float | None = sigma
+        self._setup(device, SeparableTaps.from_sigma(lib.tdk_sharpen_weights, float(sigma), 0.25, 4.0, TDK_SHARPEN_MAX_RADIUS), amount, threshold, luma, overshoot)
 
     @staticmethod
     def from_weights(device: torch.device, weights, amount: float = 0.5, threshold: float = 0.0, luma: bool = True,
@@ -47,17 +40,13 @@ class Sharpen:
         """A caller's own symmetric kernel: weights (w0, w1, .. wR), 1 <= R <= 12, finite and >= 0, used as float32.  They are
         taken as they are; a blur that keeps a flat area flat needs w0 + 2 (w1 + .. + wR) = 1."""
         self = Sharpen.__new__(Sharpen)
-        weights = tuple(ctypes.c_float(float(w)).value for w in weights)
         self._setup(device, weights, amount, threshold, luma, overshoot)
-        self.sigma = None
         return self
 
     def _setup(self, device, weights, amount, threshold, luma, overshoot) -> None:
         require_cuda_device(device)
-        if not 2 <= len(weights) <= TDK_SHARPEN_MAX_RADIUS + 1:
-            raise ValueError(f'weights must hold 2..{TDK_SHARPEN_MAX_RADIUS + 1} values (radius 1..{TDK_SHARPEN_MAX_RADIUS}), got {len(weights)}')
-        if not all(math.isfinite(w) and w >= 0.0 for w in weights):
-            raise ValueError(f'weights must be finite and >= 0, got {weights}')
+        self._weights = SeparableTaps.from_values(weights, TDK_SHARPEN_MAX_RADIUS, 'weights')
+        self.sigma: float | None = self._weights.sigma
         if not 0.0 <= float(amount) <= MAX_AMOUNT:
             raise ValueError(f'amount must lie in [0, {MAX_AMOUNT:g}], got {amount}')
         if not (math.isfinite(float(threshold)) and float(threshold) >= 0.0):
@@ -65,26 +54,23 @@ class Sharpen:
         if overshoot is not None and not (math.isfinite(float(overshoot)) and float(overshoot) >= 0.0):
             raise ValueError(f'overshoot must be None or finite and >= 0, got {overshoot}')
         self._device = device
-        self._weights = weights
-        self._c_weights = (ctypes.c_float * len(weights))(*weights)
         self.amount, self.threshold, self.luma = float(amount), float(threshold), bool(luma)
         self.overshoot = None if overshoot is None else float(overshoot)
 
     @property
     def weights(self) -> tuple[float, ...]:
         """The taps w0 .. wR as float32 values."""
-        return self._weights
+        return self._weights.values
 
     @property
     def radius(self) -> int:
-        return len(self._weights) - 1
+        return self._weights.radius
 
     def _flags(self, channels: int) -> int:
         return (TDK_SHARPEN_LUMA if self.luma and channels == 3 else 0) | (TDK_SHARPEN_LIMIT if self.overshoot is not None else 0)
 
     def __repr__(self):
-        kernel = f'sigma={self.sigma:g}' if self.sigma is not None else f'weights={self._weights}'
-        return f'Sharpen({kernel}, radius={self.radius}, amount={self.amount:g}, threshold={self.threshold:g}, luma={self.luma}, overshoot={self.overshoot})'
+        return f'Sharpen({self._weights!r}, radius={self.radius}, amount={self.amount:g}, threshold={self.threshold:g}, luma={self.luma}, overshoot={self.overshoot})'
 
     def lds_bytes(self, channels: int, dtype: torch.dtype) -> int:
         """LDS one workgroup takes on frames of this kind (0: not a legal call)."""
@@ -95,7 +81,7 @@ class Sharpen:
         height, width, channels, tag = check_frame(image)
         with torch.cuda.device(image.device):
             out = torch.empty_like(image)
-            rc = lib.tdk_sharpen(_ptr(image), _ptr(out), width, height, channels, tag, self._c_weights, self.radius, self.amount,
+            rc = lib.tdk_sharpen(_ptr(image), _ptr(out), width, height, channels, tag, self._weights.c_array, self.radius, self.amount,
                                  self.threshold, 0.0 if self.overshoot is None else self.overshoot, self._flags(channels), _stream())
         check(rc)
         return out

@@ -22,23 +22,18 @@ every call: an in-place update (a new `NoiseProfile.estimate` copied into `noise
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
 from ._frames import MAX_SIZE, require_cuda_device
 from ._native import TDK_F16, TDK_F32, TDK_TEMPORAL_HEAD_BYTES, TDK_TEMPORAL_MAX_FRAMES, TDK_TEMPORAL_TILE_H, TDK_TEMPORAL_TILE_W, check, lib
+from ._stage import as_float32 as _f32
 from .bayer import BayerPattern
 from .noiseprofile import NoiseModel
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
 _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
-
-
-def _f32(value) -> float:
-    """The float32 nearest `value`, as a Python float."""
-    return ctypes.c_float(float(value)).value
 
 
 class TemporalDenoise:

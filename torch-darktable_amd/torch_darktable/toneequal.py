@@ -22,24 +22,22 @@ capturable in a HIP graph from the first call, and bit-reproducible.
 
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from ._frames import TAGS, check_frame, check_size, require_cuda_device
-from ._native import TDK_F16, TDK_F32, TDK_TONEEQ_EV_MAX, TDK_TONEEQ_EV_MIN, TDK_TONEEQ_MAX_RADIUS, TDK_TONEEQ_STEPS, TDK_TONEEQ_TABLE, check, lib
-from ._streams import StreamBuffers
+from ._frames import TAGS
+from ._native import TDK_TONEEQ_EV_MAX, TDK_TONEEQ_EV_MIN, TDK_TONEEQ_MAX_RADIUS, TDK_TONEEQ_STEPS, TDK_TONEEQ_TABLE, check, lib
+from ._stage import FrameStage, as_float32, luma_weights
 from .torch_darktable_extension import _ptr, _stream
 
-REC709 = (0.2126, 0.7152, 0.0722)
 CENTRES = tuple(float(c) for c in range(-8, 1))   # the nine bands, in EV
 CELLS = (2, 4, 8, 16)
 MAX_OVERSHOOT_EV = 1.0   # how far the curve may leave the range of its nodes between them
 
 
-class ToneEqualizer:
+class ToneEqualizer(FrameStage):
     """Dodge and burn (H, W, 3) frames of one size (width, height).  gains_ev: nine gains in EV for the bands at -8 .. 0 EV;
     mask_exposure: EV added to the mask in front of the curve (places the frame's tones on the bands)."""
 
@@ -47,34 +45,23 @@ class ToneEqualizer:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], gains_ev=(0,) * 9, cell: int = 8, radius: int = 4, eps: float = 1e-4,
                  mask_exposure: float = 0.0, sigma: float = 2 ** 0.5, weights=None):
-        require_cuda_device(device)
-        check_size('Image', image_size)
+        super().__init__(device, image_size)
         if cell not in CELLS:
             raise ValueError(f'cell must be one of {CELLS}, got {cell}')
         if int(radius) != radius or not 0 <= int(radius) <= TDK_TONEEQ_MAX_RADIUS:
             raise ValueError(f'radius must be an integer in 0..{TDK_TONEEQ_MAX_RADIUS}, got {radius}')
-        eps = ctypes.c_float(float(eps)).value
+        eps = as_float32(eps)
         if not (math.isfinite(eps) and eps > 0.0):
             raise ValueError(f'eps must be finite and > 0 as a float32, got {eps}')
-        weights = REC709 if weights is None else tuple(float(v) for v in weights)
-        if len(weights) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in weights):
-            raise ValueError(f'weights must be three finite values >= 0, got {weights}')
+        self.weights, self._c_weights = luma_weights(weights)
         if not (math.isfinite(float(sigma)) and float(sigma) > 0.0):
             raise ValueError(f'sigma must be finite and > 0, got {sigma}')
-        self._device = device
-        self.width, self.height = int(image_size[0]), int(image_size[1])
         self.cell, self.radius, self.eps, self.sigma = int(cell), int(radius), eps, float(sigma)
-        self.weights = tuple(ctypes.c_float(v).value for v in weights)
-        self._c_weights = (ctypes.c_float * 3)(*self.weights)
         self._gains_ev, self.mask_exposure = self._check_gains(gains_ev, mask_exposure)
         # the table on the host, kept by the object: set_gains fills it and copies it to the device in stream order
         self._host_table = torch.from_numpy(self.make_table(self._gains_ev, self.mask_exposure, self.sigma))
-        self._table: torch.Tensor | None = None
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            where = torch.device('cuda', torch.cuda.current_device()) if device.index is None else device
-            self._table = self._host_table.to(where)
-            self._workspace(where)
+        where = self._prepare()
+        self._table: torch.Tensor | None = None if where is None else self._host_table.to(where)
 
     # ---- the curve, on the host in float64
     @staticmethod
@@ -140,10 +127,6 @@ class ToneEqualizer:
     def gains_ev(self) -> tuple[float, ...]:
         return self._gains_ev
 
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
-
     def __repr__(self):
         return (f'ToneEqualizer({self.width}x{self.height}, gains_ev={self._gains_ev}, cell={self.cell}, radius={self.radius}, eps={self.eps:g}, '
                 f'mask_exposure={self.mask_exposure:g})')
@@ -155,18 +138,8 @@ class ToneEqualizer:
         """The largest LDS use of a workgroup over the launches of a call on frames of this type (0: not a legal call)."""
         return int(lib.tdk_toneeq_lds_bytes(TAGS.get(dtype, -1), self.cell, self.radius))
 
-    def _workspace(self, device: torch.device) -> torch.Tensor:
-        """The three cell planes between the launches, one buffer per stream: the object may be used from several streams at once.
-        The buffer of the stream current at construction exists from then on, so a capture allocates nothing.  Every value read was
-        written by the same call: the buffer is never cleared."""
-        return self._workspaces.get(self.workspace_bytes(), device)
-
     def _run(self, image: torch.Tensor, want_frame: bool, want_mask: bool):
-        height, width, channels, tag = check_frame(image, (self.height, self.width), 'ToneEqualizer')
-        if channels != 3:
-            raise ValueError(f'image channels must be 3, got {channels}')
-        if tag not in (TDK_F32, TDK_F16):
-            raise ValueError(f'image must be float32 or float16, got {image.dtype}')
+        height, width, _, tag = self._float_frame(image, 'ToneEqualizer', 'image channels must be 3')
         if self._table is None or self._table.device != image.device:
             raise RuntimeError(f'ToneEqualizer was built for {None if self._table is None else self._table.device}, the image is on {image.device}')
         with torch.cuda.device(image.device):

@@ -22,13 +22,10 @@ import torch
 
 from ._frames import TAGS, check_frame, check_size, require_cuda_device
 from ._native import TDK_WAVELET_MAX_SCALES, TDK_WAVELET_YCC, check, lib
+from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .extension import extension
 from .torch_darktable_extension import _ptr, _stream
-
-
-def _f32(v: float) -> float:
-    return ctypes.c_float(float(v)).value
 
 
 def band_norms(scales: int) -> tuple[float, ...]:
