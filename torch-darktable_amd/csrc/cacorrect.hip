@@ -23,7 +23,6 @@ namespace {
 
 constexpr int CA_TW = TDK_CA_TILE_W, CA_TH = TDK_CA_TILE_H;
 constexpr int CA_THREADS = 256;
-constexpr int CA_MAX_SIZE = 65535;
 constexpr int CA_D = TDK_CA_MAX_SHIFT;
 constexpr int CA_SUMS = TDK_CA_SUMS;
 constexpr int CA_TERMS = 10;   // per colour the nine sums of step 3 and the number of kept blocks
@@ -364,11 +363,7 @@ int ca_launch_finish(const CaFinishArgs& a, hipStream_t st) {
   return TDK_OK;
 }
 
-bool ca_pattern_ok(uint32_t pattern) {
-  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
-}
 bool ca_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
-bool ca_size_ok(int width, int height) { return width >= 2 && height >= 2 && width <= CA_MAX_SIZE && height <= CA_MAX_SIZE; }
 bool ca_block_ok(int block) { return block >= 16 && block <= 256 && block % 2 == 0; }
 
 }  // namespace
@@ -385,9 +380,9 @@ TDK_EXPORT int tdk_ca_correct(const void* src, int src_dtype, void* out, int out
   static const char* const who = "tdk_ca_correct";
   TDK_REQUIRE(src && out && model, "%s: null pointer (src, out or model)", who);
   TDK_REQUIRE(ca_dtype_ok(src_dtype) && ca_dtype_ok(out_dtype), "%s: unsupported dtype tags %d -> %d", who, src_dtype, out_dtype);
-  TDK_REQUIRE(ca_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, CA_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
-  TDK_REQUIRE(ca_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+  TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
   TDK_REQUIRE(interp == TDK_CA_BILINEAR || interp == TDK_CA_BICUBIC, "%s: interp must be 0 (bilinear) or 1 (bicubic), got %d", who, interp);
   TDK_REQUIRE(isfinite(x0) && isfinite(y0), "%s: the centre must be finite", who);
   TDK_REQUIRE(isfinite(rn) && rn > 0.0f, "%s: rn must be finite and > 0", who);
@@ -404,7 +399,7 @@ TDK_EXPORT int tdk_ca_correct(const void* src, int src_dtype, void* out, int out
 }
 
 TDK_EXPORT size_t tdk_ca_workspace_bytes(int width, int height, int block) {
-  if (!ca_size_ok(width, height) || width % 2 || height % 2 || !ca_block_ok(block)) return 0;
+  if (!tdk_mosaic_size_ok(width, height) || width % 2 || height % 2 || !ca_block_ok(block)) return 0;
   const size_t blocks = (size_t)(width / block) * (size_t)(height / block);
   const size_t bytes = blocks * 2 * CA_SUMS * sizeof(long long);
   return bytes < 16 ? 16 : bytes;
@@ -418,9 +413,9 @@ TDK_EXPORT int tdk_ca_estimate(const void* const* frames, int num_frames, int sr
   TDK_REQUIRE(num_frames >= 1 && num_frames <= TDK_CA_MAX_FRAMES, "%s: num_frames must be 1..%d, got %d", who, TDK_CA_MAX_FRAMES, num_frames);
   for (int f = 0; f < num_frames; f++) TDK_REQUIRE(frames[f], "%s: null pointer (frame %d)", who, f);
   TDK_REQUIRE(ca_dtype_ok(src_dtype), "%s: unsupported dtype tag %d", who, src_dtype);
-  TDK_REQUIRE(ca_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, CA_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
-  TDK_REQUIRE(ca_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+  TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
   TDK_REQUIRE(fit == TDK_CA_LINEAR || fit == TDK_CA_POLY3, "%s: fit must be 0 (linear) or 1 (poly3), got %d", who, fit);
   TDK_REQUIRE(isfinite(clip) && clip > 0.0f, "%s: clip must be finite and > 0", who);
   TDK_REQUIRE(ca_block_ok(block), "%s: block must be even, 16..256, got %d", who, block);

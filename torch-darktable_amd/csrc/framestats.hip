@@ -33,7 +33,6 @@ constexpr int FS_UNIT = 16;                                 // pixels (columns o
 constexpr int FS_MAX_COPIES = 16;
 constexpr int FS_HIST_WORDS = FS_MAX_COPIES * (3 * 256 + 1);  // 16 copies of 3 x 256 bins, 4 of 3 x 1024
 constexpr int FS_COUNTERS = 5;                              // below, above, nan, valid, sum: the order in a record and in `counts`
-constexpr int FS_MAX_SIZE = 65535;
 constexpr int FS_RED_IDX = 32, FS_RED_LANES = FS_THREADS / FS_RED_IDX;   // fs_reduce: counters of a workgroup, lanes per counter
 constexpr int FS_DER_THREADS = 256, FS_DER_BINS = TDK_STATS_MAX_BINS / FS_DER_THREADS;
 constexpr size_t FS_WS_ALIGN = 8;
@@ -340,9 +339,6 @@ __global__ __launch_bounds__(FS_DER_THREADS) void fs_derive(const long long* __r
   }
 }
 
-bool fs_pattern_ok(uint32_t pattern) {
-  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
-}
 bool fs_shape_ok(int bins, int channels) { return bins >= 2 && bins <= TDK_STATS_MAX_BINS && (channels == 1 || channels == 3); }
 size_t fs_dtype_bytes(int dtype) { return dtype == TDK_F32 ? 4 : (dtype == TDK_F16 || dtype == TDK_U16) ? 2 : 1; }
 
@@ -384,14 +380,14 @@ TDK_EXPORT int tdk_framestats(const void* const* frames, int num_frames, int dty
   TDK_REQUIRE(num_frames >= 1 && num_frames <= TDK_STATS_MAX_FRAMES, "%s: num_frames must be 1..%d, got %d", who, TDK_STATS_MAX_FRAMES, num_frames);
   for (int f = 0; f < num_frames; f++) TDK_REQUIRE(frames[f], "%s: null pointer (frames[%d])", who, f);
   TDK_REQUIRE(dtype == TDK_F32 || dtype == TDK_F16 || dtype == TDK_U8 || dtype == TDK_U16, "%s: unsupported dtype tag %d", who, dtype);
-  TDK_REQUIRE(width >= 1 && height >= 1 && width <= FS_MAX_SIZE && height <= FS_MAX_SIZE, "%s: frame size %dx%d outside 1..%d", who, width, height, FS_MAX_SIZE);
+  TDK_REQUIRE(tdk_frame_size_ok(width, height), "%s: frame size %dx%d outside 1..%d", who, width, height, TDK_FRAME_MAX_SIZE);
   TDK_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, channels);
   if (pattern != 0u) {
-    TDK_REQUIRE(fs_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+    TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
     TDK_REQUIRE(channels == 3, "%s: a mosaic has channels = 3 (R, G, B), got %d", who, channels);
     TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
   }
-  TDK_REQUIRE(stride >= 1 && stride <= FS_MAX_SIZE, "%s: stride must be 1..%d, got %d", who, FS_MAX_SIZE, stride);
+  TDK_REQUIRE(stride >= 1 && stride <= TDK_FRAME_MAX_SIZE, "%s: stride must be 1..%d, got %d", who, TDK_FRAME_MAX_SIZE, stride);
   TDK_REQUIRE(bins >= 2 && bins <= TDK_STATS_MAX_BINS, "%s: bins must be 2..%d, got %d", who, TDK_STATS_MAX_BINS, bins);
   const float range = hi - lo, scale = (float)bins / range;
   TDK_REQUIRE(isfinite(lo) && isfinite(hi) && lo < hi && isfinite(range) && isfinite(scale), "%s: the range needs finite lo < hi with a finite bins / (hi - lo)", who);

@@ -36,7 +36,6 @@ constexpr int HL_PITCH = HL_TW + 2 * HL_APRON, HL_SROWS = HL_TH + 2 * HL_APRON; 
 constexpr int HL_CELLS_X = HL_PITCH / 2, HL_CELLS_Y = HL_SROWS / 2;               // ... as 10 rows of 66 cells
 constexpr int HL_QUADS = HL_TW / 4;                                               // a thread's block is 2 rows x 4 columns
 constexpr int HL_GROUPS = 256;                                                    // workgroups, and records, of the statistics launch
-constexpr int HL_MAX_SIZE = 65535;
 constexpr size_t HL_WS_ALIGN = 8;
 static_assert(HL_THREADS == (HL_TH / 2) * HL_QUADS, "a thread per 2 x 4 sites of the tile");
 static_assert(HL_GROUPS == HL_THREADS, "the apply launch reads a record per thread");
@@ -389,18 +388,15 @@ int launch_apply(const void* src, void* dst, const float* gains, void* workspace
   return TDK_OK;
 }
 
-bool hl_pattern_ok(uint32_t pattern) {
-  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
-}
 
 // the checks both entry points share; `who` is the entry point's name
 int hl_check(const char* who, const void* src, int src_dtype, int width, int height, uint32_t pattern, const float* gains, float threshold, float low, int min_count) {
   TDK_REQUIRE(src, "%s: null pointer (src)", who);
   TDK_REQUIRE(gains, "%s: null pointer (gains)", who);
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= HL_MAX_SIZE && height <= HL_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, HL_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: frame size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
   TDK_REQUIRE(src_dtype == TDK_F32 || src_dtype == TDK_F16, "%s: unsupported dtype tag %d (src)", who, src_dtype);
-  TDK_REQUIRE(hl_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+  TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
   TDK_REQUIRE(threshold > 0.0f && threshold <= 1.0f, "%s: threshold must lie in (0, 1]", who);
   TDK_REQUIRE(low >= 0.0f && low < 1.0f, "%s: low must lie in [0, 1)", who);
   TDK_REQUIRE(min_count >= 1, "%s: min_count must be >= 1, got %d", who, min_count);

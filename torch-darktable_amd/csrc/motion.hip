@@ -211,7 +211,7 @@ TDK_EXPORT int tdk_motion_match(const void* pyramid_cur, int which_cur, const vo
                                 uint32_t zero_bias, const uint32_t* index, int16_t* field, uint32_t* costs, tdk_stream_t stream) {
   static const char* const who = "tdk_motion_match";
   TDK_REQUIRE(pyramid_cur && pyramid_ref && field, "%s: null pointer (pyramid_cur, pyramid_ref or field)", who);
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= MT_MAX_SIZE && height <= MT_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, MT_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
   TDK_REQUIRE(mo_levels_ok(levels), "%s: levels must be 1..%d, got %d", who, TDK_MOTION_MAX_LEVELS, levels);
   TDK_REQUIRE(search >= 1 && search <= TDK_MOTION_MAX_SEARCH, "%s: search must be 1..%d, got %d", who, TDK_MOTION_MAX_SEARCH, search);

@@ -40,7 +40,6 @@ constexpr int NP_MAX_TILES = 16;                              // tiles of a unit
 constexpr int NP_LEVELS = TDK_NOISE_LEVELS;
 constexpr int NP_HIST_WORDS = 3 * TDK_NOISE_MAX_BINS * NP_LEVELS;
 constexpr int NP_COUNTERS = 9;                                // all, nan, clipped: [which * 3 + colour]
-constexpr int NP_MAX_SIZE = 65535;
 constexpr int NP_RED_IDX = 32, NP_RED_LANES = NP_THREADS / NP_RED_IDX;   // np_reduce: counters of a workgroup, lanes per counter
 constexpr int NP_DER_THREADS = 128;
 constexpr size_t NP_WS_ALIGN = 8;
@@ -407,9 +406,6 @@ __global__ __launch_bounds__(NP_VST_THREADS) void np_vst(const TS* __restrict__ 
   }
 }
 
-bool np_pattern_ok(uint32_t pattern) {
-  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
-}
 bool np_bins_ok(int bins) { return bins >= 2 && bins <= TDK_NOISE_MAX_BINS; }
 size_t np_dtype_bytes(int dtype) { return dtype == TDK_F32 ? 4 : 2; }
 size_t np_rec_bytes(int bins) { return (size_t)3 * bins * NP_LEVELS * 4 + (size_t)(3 * bins + NP_COUNTERS) * 8; }
@@ -438,11 +434,11 @@ int np_transform(const char* who, const void* src, int src_dtype, void* dst, int
   TDK_REQUIRE(count >= 1, "%s: count must be >= 1, got %lld", who, (long long)count);
   TDK_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, channels);
   if (pattern != 0u) {
-    TDK_REQUIRE(np_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+    TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
     TDK_REQUIRE(channels == 1, "%s: a mosaic has channels = 1, got %d", who, channels);
-    TDK_REQUIRE(width >= 2 && width <= NP_MAX_SIZE && width % 2 == 0, "%s: mosaic width must be even, 2..%d, got %d", who, NP_MAX_SIZE, width);
-    TDK_REQUIRE(count % width == 0 && count / width <= NP_MAX_SIZE && (count / width) % 2 == 0, "%s: a mosaic of width %d holds an even number of rows, at most %d; count is %lld",
-                who, width, NP_MAX_SIZE, (long long)count);
+    TDK_REQUIRE(width >= 2 && width <= TDK_MOSAIC_MAX_SIZE && width % 2 == 0, "%s: mosaic width must be even, 2..%d, got %d", who, TDK_MOSAIC_MAX_SIZE, width);
+    TDK_REQUIRE(count % width == 0 && count / width <= TDK_MOSAIC_MAX_SIZE && (count / width) % 2 == 0, "%s: a mosaic of width %d holds an even number of rows, at most %d; count is %lld",
+                who, width, TDK_MOSAIC_MAX_SIZE, (long long)count);
   } else {
     TDK_REQUIRE(count % channels == 0, "%s: count %lld is no multiple of channels = %d", who, (long long)count, channels);
   }
@@ -474,9 +470,9 @@ TDK_EXPORT int tdk_noise_profile(const void* const* frames, int num_frames, int 
   TDK_REQUIRE(num_frames >= 1 && num_frames <= TDK_NOISE_MAX_FRAMES, "%s: num_frames must be 1..%d, got %d", who, TDK_NOISE_MAX_FRAMES, num_frames);
   for (int f = 0; f < num_frames; f++) TDK_REQUIRE(frames[f], "%s: null pointer (frames[%d])", who, f);
   TDK_REQUIRE(dtype == TDK_F32 || dtype == TDK_F16 || dtype == TDK_U16, "%s: unsupported dtype tag %d", who, dtype);
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= NP_MAX_SIZE && height <= NP_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, NP_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
-  TDK_REQUIRE(np_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+  TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
   TDK_REQUIRE(np_bins_ok(bins), "%s: bins must be 2..%d, got %d", who, TDK_NOISE_MAX_BINS, bins);
   const float scale = 65535.0f / white;
   TDK_REQUIRE(isfinite(white) && white > 0.0f && isfinite(scale), "%s: white must be finite and > 0 with a finite 65535 / white", who);

@@ -31,7 +31,7 @@ constexpr int RP_PITCH = RP_TW + 2 * RP_APRON, RP_SROWS = RP_TH + 2 * RP_APRON; 
 constexpr int RP_PAIRS = RP_PITCH / 2;
 // grid nodes under a tile: nodes are at least four pixels apart, so 128 columns meet at most 33 first nodes and their successors
 constexpr int RP_NX = 36, RP_NY = 8;
-constexpr int RP_MAX_SIZE = 65535, RP_MAX_GRID = 257;
+constexpr int RP_MAX_GRID = 257;
 static_assert(RP_THREADS == RP_GROUPS * RP_TH, "a thread per 8 pixels of the tile");
 static_assert(RP_TW / 4 + 2 <= RP_NX && RP_TH / 4 + 2 <= RP_NY, "node box");
 
@@ -371,13 +371,11 @@ TDK_EXPORT int tdk_raw_prepare(const void* src, int src_format, void* dst, int d
                                int grid_width, int grid_height, const float* gains, int clip, tdk_stream_t stream) {
   TDK_REQUIRE(src && dst, "tdk_raw_prepare: null pointer (src or dst)");
   TDK_REQUIRE(black && scale, "tdk_raw_prepare: null pointer (black or scale)");
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= RP_MAX_SIZE && height <= RP_MAX_SIZE, "tdk_raw_prepare: frame size %dx%d outside 2..%d", width, height,
-              RP_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "tdk_raw_prepare: frame size %dx%d outside 2..%d", width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "tdk_raw_prepare: frame size %dx%d must be even in both axes (whole CFA cells)", width, height);
   TDK_REQUIRE(src_format >= TDK_RAW_PACKED12 && src_format <= TDK_RAW_F16, "tdk_raw_prepare: unknown src_format %d", src_format);
   TDK_REQUIRE(dst_dtype == TDK_F32 || dst_dtype == TDK_F16, "tdk_raw_prepare: unsupported dtype tag %d", dst_dtype);
-  TDK_REQUIRE(pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG,
-              "tdk_raw_prepare: unknown Bayer pattern 0x%08x", pattern);
+  TDK_REQUIRE(tdk_pattern_ok(pattern), "tdk_raw_prepare: unknown Bayer pattern 0x%08x", pattern);
   for (int p = 0; p < 4; p++) {
     TDK_REQUIRE(isfinite(black[p]), "tdk_raw_prepare: black[%d] is not finite", p);
     TDK_REQUIRE(isfinite(scale[p]), "tdk_raw_prepare: scale[%d] is not finite", p);

@@ -1,7 +1,9 @@
 // tdk_frame.h -- host-side argument helpers of the frame operators: resample, warp, sharpen, nlmeans, rawprepare on frames of TDK_F32 |
 // TDK_F16 | TDK_U8 elements with 1 or 3 interleaved channels, and the stages bound to one frame size (toneequal, dehaze, filmic, deconv,
 // lmmse, defringe) on TDK_F32 | TDK_F16.  The helpers answer a question; the message of a failed check stays with the entry point
-// that reports it.  The one exception is tdk_gaussian_taps, the whole body of the three tdk_*_weights entry points.
+// that reports it.  The one exception is tdk_gaussian_taps, the whole body of the three tdk_*_weights entry points.  The stages on raw
+// (H, W) mosaics (rawprepare, highlights, cacorrect, noiseprofile, framestats and the tile kernels of tdk_mosaic_tile.h) ask for a
+// pattern and a mosaic size here.
 #pragma once
 
 #include "../../include/tdk_hip_resample.h"   // TDK_U8
@@ -12,6 +14,12 @@
 constexpr int TDK_FRAME_MAX_SIZE = 65535;   // the largest width and height of a frame
 
 static inline bool tdk_frame_size_ok(int width, int height) { return width >= 1 && height >= 1 && width <= TDK_FRAME_MAX_SIZE && height <= TDK_FRAME_MAX_SIZE; }
+constexpr int TDK_MOSAIC_MAX_SIZE = TDK_FRAME_MAX_SIZE;   // of a raw mosaic, whose smallest side is one CFA cell
+
+static inline bool tdk_mosaic_size_ok(int width, int height) { return width >= 2 && height >= 2 && width <= TDK_MOSAIC_MAX_SIZE && height <= TDK_MOSAIC_MAX_SIZE; }
+static inline bool tdk_pattern_ok(uint32_t pattern) {
+  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
+}
 static inline bool tdk_float_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
 static inline size_t tdk_dtype_bytes(int dtype) { return dtype == TDK_F32 ? 4 : dtype == TDK_F16 ? 2 : 1; }
 

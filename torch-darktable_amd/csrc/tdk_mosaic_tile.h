@@ -9,7 +9,6 @@
 #include "tdk_frame.h"
 
 constexpr int MT_THREADS = 256;   // lanes of a workgroup
-constexpr int MT_MAX_SIZE = 65535;
 
 // ---- storage: M consecutive elements at p, as float32.  One or two 16-byte vectors (8 bytes for four binary16) when p is on such a
 // boundary, per element otherwise.
@@ -190,20 +189,15 @@ __device__ __forceinline__ float mt_similarity(float E, float V, float e, float 
 }
 
 // ---- host side
-static inline bool mt_pattern_ok(uint32_t pattern) {
-  return pattern == TDK_PATTERN_RGGB || pattern == TDK_PATTERN_BGGR || pattern == TDK_PATTERN_GRBG || pattern == TDK_PATTERN_GBRG;
-}
 static inline bool mt_dtype_ok(int dtype) { return dtype == TDK_F32 || dtype == TDK_F16; }
-static inline bool mt_size_ok(int width, int height) {
-  return width >= 2 && height >= 2 && width <= MT_MAX_SIZE && height <= MT_MAX_SIZE && width % 2 == 0 && height % 2 == 0;
-}
+static inline bool mt_size_ok(int width, int height) { return tdk_mosaic_size_ok(width, height) && width % 2 == 0 && height % 2 == 0; }
 static inline size_t mt_plane_bytes(int width, int height, size_t element) { return tdk_align_up((size_t)width * (size_t)height * element, 16); }
 
 // the size of a mosaic, its pattern and the radius of the window
 static inline int mt_check_mosaic(const char* who, int width, int height, uint32_t pattern, int radius) {
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= MT_MAX_SIZE && height <= MT_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, MT_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
-  TDK_REQUIRE(mt_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
+  TDK_REQUIRE(tdk_pattern_ok(pattern), "%s: unknown Bayer pattern 0x%08x", who, pattern);
   TDK_REQUIRE(radius == 2 || radius == 3, "%s: radius must be 2 or 3, got %d", who, radius);
   return TDK_OK;
 }

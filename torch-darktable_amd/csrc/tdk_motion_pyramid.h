@@ -135,7 +135,7 @@ static inline int mo_check_pyramid(const char* who, const void* src, int src_dty
                                    const uint32_t* index, int which, MoPyramidArgs& a) {
   TDK_REQUIRE(src && pyramid, "%s: null pointer (src or pyramid)", who);
   TDK_REQUIRE(mt_dtype_ok(src_dtype), "%s: unsupported dtype tag %d", who, src_dtype);
-  TDK_REQUIRE(width >= 2 && height >= 2 && width <= MT_MAX_SIZE && height <= MT_MAX_SIZE, "%s: frame size %dx%d outside 2..%d", who, width, height, MT_MAX_SIZE);
+  TDK_REQUIRE(tdk_mosaic_size_ok(width, height), "%s: frame size %dx%d outside 2..%d", who, width, height, TDK_MOSAIC_MAX_SIZE);
   TDK_REQUIRE(width % 2 == 0 && height % 2 == 0, "%s: mosaic size %dx%d must be even in both axes (whole CFA cells)", who, width, height);
   TDK_REQUIRE(isfinite(scale) && scale > 0.0f, "%s: scale must be finite and > 0", who);
   TDK_REQUIRE(mo_levels_ok(levels), "%s: levels must be 1..%d, got %d", who, TDK_MOTION_MAX_LEVELS, levels);

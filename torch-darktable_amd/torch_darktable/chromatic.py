@@ -25,21 +25,20 @@ import math
 
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
+from ._mosaic import FLOAT_TAGS, MosaicStage, check_frame_set, check_pattern, check_storage, out_dtype_of
 from ._native import (TDK_CA_BICUBIC, TDK_CA_BILINEAR, TDK_CA_LINEAR, TDK_CA_MAX_FRAMES, TDK_CA_MAX_SHIFT, TDK_CA_POLY3, TDK_CA_SUMS, TDK_CA_TILE_H, TDK_CA_TILE_W,
-                      TDK_F16, TDK_F32, check, lib)
+                      check, lib)
 from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .noiseprofile import NoiseModel
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _INTERPS = {'bilinear': TDK_CA_BILINEAR, 'bicubic': TDK_CA_BICUBIC}
 _FITS = {'linear': TDK_CA_LINEAR, 'poly3': TDK_CA_POLY3}
 
 
-class ChromaticAberration:
+class ChromaticAberration(MosaicStage):
     """The model of one camera and the two operations on it; image_size is (width, height), both even.  `model`: a contiguous (2, 4)
     float32 tensor, rows red and blue, columns v, c, b, valid (None: the identity, created on first use on the device of the input);
     `center`: the optical centre (x0, y0) in site coordinates, None: ((W-1)/2, (H-1)/2); `rn`: the radius at which rho is 1, None: the
@@ -53,14 +52,10 @@ class ChromaticAberration:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, model: torch.Tensor | None = None,
                  center: tuple[float, float] | None = None, rn: float | None = None, interp: str = 'bilinear'):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if not isinstance(bayer_pattern, BayerPattern):
-            raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Mosaic dimensions must be even (whole CFA cells), got {width}x{height}')
+        super().__init__(device, image_size)
+        check_pattern(bayer_pattern)
+        self._check_even()
+        width, height = self.width, self.height
         if interp not in _INTERPS:
             raise ValueError(f"interp must be 'bilinear' or 'bicubic', got {interp!r}")
         if center is None:
@@ -77,22 +72,17 @@ class ChromaticAberration:
             raise ValueError(f'rn must be finite and > 0, got {rn}')
         if model is not None:
             self._check_model(model)
-        self._device = device
-        self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
+        self.bayer_pattern = bayer_pattern
         self.center, self.rn, self.interp = (x0, y0), rn, interp
         self._model = model
         self._workspaces = StreamBuffers()   # of `estimate`, per block size and stream; shared with the objects `estimate` returns
         if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            self._workspace(64, torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
+            self._workspace(64, self._home_device())
 
     @staticmethod
     def _check_model(model) -> None:
         if not isinstance(model, torch.Tensor) or tuple(model.shape) != (2, 4) or model.dtype != torch.float32 or not model.is_contiguous():
             raise ValueError(f'model must be a contiguous (2, 4) float32 tensor, got {tuple(getattr(model, "shape", ()))} {getattr(model, "dtype", type(model).__name__)}')
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
 
     @property
     def model(self) -> torch.Tensor | None:
@@ -137,7 +127,7 @@ class ChromaticAberration:
 
     def lds_bytes(self, src_dtype: torch.dtype = torch.float32) -> int:
         """Static LDS of a workgroup of `correct`: the staged source box."""
-        return int(lib.tdk_ca_lds_bytes(_INTERPS[self.interp], _TAGS.get(src_dtype, -1)))
+        return int(lib.tdk_ca_lds_bytes(_INTERPS[self.interp], FLOAT_TAGS.get(src_dtype, -1)))
 
     def workspace_bytes(self, block: int = 64) -> int:
         return int(lib.tdk_ca_workspace_bytes(self.width, self.height, int(block)))
@@ -167,16 +157,12 @@ class ChromaticAberration:
         """An (H, W) mosaic, float32 or float16, contiguous -> a fresh tensor: green as it is, red and blue taken from where the model
         says they were captured.  model: a (2, 4) tensor or a ChromaticAberration; None: the object's own."""
         self._check_frame(mosaic, 'input')
-        out_dtype = mosaic.dtype if out_dtype is None else out_dtype
-        if out_dtype not in _TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
-        _require(mosaic.is_cuda, 'Input must be on CUDA device')
-        _require(mosaic.is_contiguous(), 'Input must be contiguous')
-        _require(mosaic.dtype in _TAGS, 'Input tensor must be float32 or float16')
+        out_dtype = out_dtype_of(out_dtype, mosaic.dtype)
+        check_storage(mosaic)
         with torch.cuda.device(mosaic.device):
             model = self._model_of(model, mosaic.device)
             out = torch.empty(mosaic.shape, dtype=out_dtype, device=mosaic.device)
-            rc = lib.tdk_ca_correct(_ptr(mosaic), _TAGS[mosaic.dtype], _ptr(out), _TAGS[out_dtype], self.width, self.height, _pattern(self.bayer_pattern),
+            rc = lib.tdk_ca_correct(_ptr(mosaic), FLOAT_TAGS[mosaic.dtype], _ptr(out), FLOAT_TAGS[out_dtype], self.width, self.height, _pattern(self.bayer_pattern),
                                     _ptr(model), self.center[0], self.center[1], self.rn, _INTERPS[self.interp], _stream())
         check(rc)
         return out
@@ -210,11 +196,7 @@ class ChromaticAberration:
         frames = self._frames(mosaics)
         clip, block, max_shift = self._estimate_arguments(noise_model, fit, clip, block, max_shift)
         first = frames[0]
-        for frame in frames:
-            _require(frame.is_cuda, 'Input must be on CUDA device')
-            _require(frame.is_contiguous(), 'Input must be contiguous')
-            _require(frame.dtype in _TAGS and frame.dtype == first.dtype, 'Input tensors must be all float32 or all float16')
-            _require(frame.device == first.device, 'The frames must be on one device')
+        check_frame_set(frames)
         noise = None if noise_model is None else noise_model.model
         if noise is not None:
             _require(noise.device == first.device, 'The noise model must be on the device of the input')
@@ -222,7 +204,7 @@ class ChromaticAberration:
         with torch.cuda.device(first.device):
             workspace = self._workspace(block, first.device)
             model = torch.empty((2, 4), dtype=torch.float32, device=first.device)
-            rc = lib.tdk_ca_estimate(pointers, len(frames), _TAGS[first.dtype], self.width, self.height, _pattern(self.bayer_pattern), _ptr(noise), _FITS[fit],
+            rc = lib.tdk_ca_estimate(pointers, len(frames), FLOAT_TAGS[first.dtype], self.width, self.height, _pattern(self.bayer_pattern), _ptr(noise), _FITS[fit],
                                      clip, block, max_shift, self.center[0], self.center[1], self.rn, _ptr(workspace), _ptr(model), _stream())
         check(rc)
         return model, workspace

@@ -25,11 +25,11 @@ from dataclasses import dataclass
 
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
+from ._frames import MAX_SIZE
+from ._mosaic import MosaicStage, check_pattern
 from ._native import (TDK_F16, TDK_F32, TDK_STATS_CHUNK, TDK_STATS_GRID, TDK_STATS_MAX_BINS, TDK_STATS_MAX_FRAMES, TDK_STATS_MAX_QUANTILES, TDK_U8, TDK_U16,
                       check, lib)
 from ._stage import as_float32 as _f32
-from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
@@ -52,7 +52,7 @@ class FrameStatistics:
     gains: torch.Tensor         # (3,) float32 grey-world gains (R, G, B), green = 1
 
 
-class FrameStats:
+class FrameStats(MosaicStage):
     """Measure frames of one size; image_size is (width, height).  `channels` (1 or 3) is for (H, W, C) images; with `bayer_pattern`
     the frames are (H, W) mosaics, width and height even, and the result has three channels."""
 
@@ -61,15 +61,10 @@ class FrameStats:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], channels: int = 3, bayer_pattern: BayerPattern | None = None, bins: int = 256,
                  value_range: tuple[float, float] = (0.0, 1.0), stride: int = 1, quantiles=(0.001, 0.5, 0.999), max_frames: int = 1, min_count: int = 64):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (1 <= width <= MAX_SIZE and 1 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 1..{MAX_SIZE}, got {width}x{height}')
+        super().__init__(device, image_size, min_size=1)
         if bayer_pattern is not None:
-            if not isinstance(bayer_pattern, BayerPattern):
-                raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
-            if width % 2 or height % 2:
-                raise ValueError(f'Mosaic dimensions must be even (whole CFA cells), got {width}x{height}')
+            check_pattern(bayer_pattern)
+            self._check_even()
             if channels != 3:
                 raise ValueError(f'a mosaic has channels = 3 (R, G, B), got {channels}')
         if channels not in (1, 3):
@@ -91,20 +86,12 @@ class FrameStats:
             raise ValueError(f'max_frames must be an integer in 1..{TDK_STATS_MAX_FRAMES}, got {max_frames}')
         if int(min_count) != min_count or not 1 <= int(min_count) < 2 ** 31:
             raise ValueError(f'min_count must be an integer >= 1, got {min_count}')
-        self._device = device
-        self.width, self.height, self.channels, self.bayer_pattern = width, height, int(channels), bayer_pattern
+        self.channels, self.bayer_pattern = int(channels), bayer_pattern
         self.bins, self.lo, self.hi, self.stride = int(bins), lo, hi, int(stride)
         self.quantiles = tuple(_f32(v) for v in q)   # the float32 fractions the kernel is given
         self.max_frames, self.min_count = int(max_frames), int(min_count)
         self._c_quantiles = (ctypes.c_float * max(len(q), 1))(*self.quantiles)
-        self._workspace_bytes = self.workspace_bytes()
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            self._workspace(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
+        self._keep_workspace()
 
     @property
     def value_range(self) -> tuple[float, float]:
@@ -122,12 +109,6 @@ class FrameStats:
     def workspace_bytes(self) -> int:
         """The records of max_frames gather launches."""
         return int(lib.tdk_framestats_workspace_bytes(self.bins, self.channels, self.max_frames))
-
-    def _workspace(self, device: torch.device) -> torch.Tensor:
-        """One buffer per stream: the object may be used from several streams at once.  The buffer of the stream current at
-        construction exists from then on, so a capture allocates nothing.  Every record a call reads it has written: the buffer is
-        never cleared."""
-        return self._workspaces.get(self._workspace_bytes, device)
 
     def _check_frames(self, frames) -> list[torch.Tensor]:
         frames = [frames] if isinstance(frames, torch.Tensor) else list(frames)

@@ -23,13 +23,13 @@ import ctypes
 
 import torch
 
-from ._native import TDK_F16, TDK_F32, check, lib
+from ._mosaic import FLOAT_TAGS
+from ._native import check, lib
 from ._streams import StreamBuffers
 from .hdrmerge import HdrMerge
 from .motion import MotionEstimate
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 # The zero preference of the matches of this block in grey-level SAD units: twice the smallest bias at which every tile of 20 static
 # noisy brackets of the synthetic chart came out zero, at exposure ratios 4 and 16 and scene gains 1 and 4 (DESIGN.md 3.23 has the
 # measurement; tests/test_hdralign_spec.py holds the 20 values below it).  The frames of a bracket differ in noise after they are
@@ -126,7 +126,7 @@ class MotionHdrMerge(HdrMerge):
         self._last = (count, first.device)
         stream = _stream()
         for f, frame in enumerate(frames):
-            check(lib.tdk_hdralign_pyramid(_ptr(frame), _TAGS[frame.dtype], self.width, self.height, me.scale, me.levels, _ptr(pyramids[f // 2]), f % 2, _ptr(exp),
+            check(lib.tdk_hdralign_pyramid(_ptr(frame), FLOAT_TAGS[frame.dtype], self.width, self.height, me.scale, me.levels, _ptr(pyramids[f // 2]), f % 2, _ptr(exp),
                                            count, f, stream))
         for f in range(count):
             if f != ref:   # cur: the anchor frame; ref of the match: frame f, so that frame_f[p + d] ~ anchor[p]
@@ -167,7 +167,7 @@ class MotionHdrMerge(HdrMerge):
             out = torch.empty(shape, dtype=out_dtype, device=first.device)
             mask = torch.empty(shape, dtype=torch.uint8, device=first.device) if return_mask else None
             pointers = (ctypes.c_void_p * count)(*[frame.data_ptr() for frame in frames])
-            rc = lib.tdk_hdralign_merge(pointers, count, _TAGS[first.dtype], _ptr(out), _TAGS[out_dtype], _ptr(mask), self.width, self.height,
+            rc = lib.tdk_hdralign_merge(pointers, count, FLOAT_TAGS[first.dtype], _ptr(out), FLOAT_TAGS[out_dtype], _ptr(mask), self.width, self.height,
                                         _pattern(self.bayer_pattern), _ptr(exp), ref, _ptr(model), self.radius, self.clip, self.thresholds[0],
                                         self.thresholds[1], self._c2, self.variance_floor, _ptr(fields), _stream())
         check(rc)

@@ -25,18 +25,16 @@ import math
 
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
-from ._native import TDK_F16, TDK_F32, TDK_HDR_MAX_FRAMES, TDK_HDR_TILE_H, TDK_HDR_TILE_W, check, lib
+from ._mosaic import FLOAT_TAGS, MosaicStage, check_frame_set, check_pattern, check_radius, out_dtype_of, positive_float32, window_repr, window_thresholds
+from ._native import TDK_HDR_MAX_FRAMES, TDK_HDR_TILE_H, TDK_HDR_TILE_W, check, lib
 from ._stage import as_float32 as _f32
 from ._streams import StreamBuffers
 from .bayer import BayerPattern
-from .noiseprofile import NoiseModel
+from .noiseprofile import NOISE_MODEL, NoiseModel
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 
-
-class HdrMerge:
+class HdrMerge(MosaicStage):
     """Merge of brackets of (H, W) mosaics of one size; image_size is (width, height), both even.  `clip`: a sample at or above it is
     clipped, and so are its eight neighbours.  `thresholds`, `pixel_threshold`, `radius` and `variance_floor` are those of
     `TemporalDenoise`: it is the same statistic, between a frame and the anchor frame of a site."""
@@ -46,60 +44,21 @@ class HdrMerge:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, noise_model: NoiseModel, radius: int = 2,
                  clip: float = 0.95, thresholds: tuple[float, float] = (1.5, 3.0), pixel_threshold: float | None = 4.0, variance_floor: float = 1e-12):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if not isinstance(bayer_pattern, BayerPattern):
-            raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Mosaic dimensions must be even (whole CFA cells), got {width}x{height}')
-        if radius not in (2, 3) or isinstance(radius, bool):
-            raise ValueError(f'radius must be 2 or 3, got {radius}')
-        clip32 = _f32(clip)
-        if not (math.isfinite(clip32) and clip32 > 0.0):
-            raise ValueError(f'clip must be finite and > 0, got {clip}')
-        if len(tuple(thresholds)) != 2:
-            raise ValueError(f'thresholds must be (t_lo, t_hi), got {thresholds}')
-        t_lo, t_hi = (_f32(v) for v in thresholds)
-        if not (math.isfinite(t_lo) and math.isfinite(t_hi) and 0.0 < t_lo < t_hi and math.isfinite(_f32(1.0 / _f32(t_hi - t_lo)))):
-            raise ValueError(f'thresholds must be finite with 0 < t_lo < t_hi, got {tuple(thresholds)}')
-        if pixel_threshold is None:
-            c2 = math.inf
-        else:
-            p = _f32(pixel_threshold)
-            c2 = _f32(p * p)
-            if not (math.isfinite(p) and p > 0.0 and c2 > 0.0):
-                raise ValueError(f'pixel_threshold must be finite and > 0, or None, got {pixel_threshold}')
-        v_min = _f32(variance_floor)
-        if not (math.isfinite(v_min) and v_min > 0.0):
-            raise ValueError(f'variance_floor must be finite and > 0, got {variance_floor}')
-        self._device = device
-        self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
-        self.radius, self.clip, self.thresholds = int(radius), clip32, (t_lo, t_hi)
-        self.pixel_threshold = None if pixel_threshold is None else _f32(pixel_threshold)
-        self._c2 = c2
-        self.variance_floor = v_min
+        super().__init__(device, image_size)
+        check_pattern(bayer_pattern)
+        self._check_even()
+        check_radius(radius)
+        self.clip = positive_float32(clip, 'clip')
+        self.thresholds, self.pixel_threshold, self._c2 = window_thresholds(thresholds, pixel_threshold)
+        self.variance_floor = positive_float32(variance_floor, 'variance_floor')
+        self.bayer_pattern, self.radius = bayer_pattern, int(radius)
         self.noise_model = noise_model
         self._exposures = StreamBuffers()   # one uploaded copy per distinct tuple of floats and stream
 
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
-
-    @property
-    def noise_model(self) -> NoiseModel:
-        return self._noise_model
-
-    @noise_model.setter
-    def noise_model(self, model: NoiseModel) -> None:
-        if not isinstance(model, NoiseModel):
-            raise TypeError(f'noise_model must be a NoiseModel, got {type(model).__name__}')
-        self._noise_model = model
+    noise_model = NOISE_MODEL
 
     def __repr__(self):
-        return (f'HdrMerge({self.width}x{self.height}, {self.bayer_pattern.name}, radius={self.radius}, clip={self.clip:g}, thresholds=({self.thresholds[0]:g}, '
-                f'{self.thresholds[1]:g}), pixel_threshold={self.pixel_threshold if self.pixel_threshold is None else format(self.pixel_threshold, "g")})')
+        return (f'HdrMerge({self.width}x{self.height}, {self.bayer_pattern.name}, radius={self.radius}, clip={self.clip:g}, {window_repr(self)})')
 
     def lds_bytes(self) -> int:
         """Static LDS of a workgroup: the staged planes, the row sums, the clip bits and the table of frames."""
@@ -148,17 +107,11 @@ class HdrMerge:
         frames = self._frames(frames)
         count = len(frames)
         first = frames[0]
-        out_dtype = first.dtype if out_dtype is None else out_dtype
-        if out_dtype not in _TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
+        out_dtype = out_dtype_of(out_dtype, first.dtype)
         if ref is not None and (isinstance(ref, bool) or int(ref) != ref or not 0 <= ref < count):
             raise ValueError(f'ref must be None or a frame index below {count}, got {ref}')
         exposures = self._exposure_values(exposures, count)
-        for frame in frames:
-            _require(frame.is_cuda, 'Input must be on CUDA device')
-            _require(frame.is_contiguous(), 'Input must be contiguous')
-            _require(frame.dtype in _TAGS and frame.dtype == first.dtype, 'Input tensors must be all float32 or all float16')
-            _require(frame.device == first.device, 'The frames must be on one device')
+        check_frame_set(frames)
         model = self._noise_model.model
         _require(model.device == first.device, 'The model must be on the device of the input')
         return frames, exposures, out_dtype, model
@@ -177,7 +130,7 @@ class HdrMerge:
             out = torch.empty(shape, dtype=out_dtype, device=first.device)
             mask = torch.empty(shape, dtype=torch.uint8, device=first.device) if return_mask else None
             pointers = (ctypes.c_void_p * count)(*[frame.data_ptr() for frame in frames])
-            rc = lib.tdk_hdr_merge(pointers, count, _TAGS[first.dtype], _ptr(out), _TAGS[out_dtype], _ptr(mask), self.width, self.height,
+            rc = lib.tdk_hdr_merge(pointers, count, FLOAT_TAGS[first.dtype], _ptr(out), FLOAT_TAGS[out_dtype], _ptr(mask), self.width, self.height,
                                    _pattern(self.bayer_pattern), _ptr(exp), -1 if ref is None else int(ref), _ptr(model), self.radius, self.clip,
                                    self.thresholds[0], self.thresholds[1], self._c2, self.variance_floor, _stream())
         check(rc)

@@ -28,32 +28,25 @@ import math
 
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
-from ._native import TDK_F16, TDK_F32, TDK_HL_CLIP, TDK_HL_OPPOSED, check, lib
-from ._streams import StreamBuffers
+from ._mosaic import FLOAT_TAGS, MosaicStage, check_pattern, out_dtype_of
+from ._native import TDK_HL_CLIP, TDK_HL_OPPOSED, check, lib
 from .bayer import BayerPattern
-from .torch_darktable_extension import _pattern, _ptr, _require, _stream
+from .torch_darktable_extension import _pattern, _ptr, _stream
 
 MAX_GAIN = 64.0
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _MODES = {'clip': TDK_HL_CLIP, 'opposed': TDK_HL_OPPOSED}
 
 
-class Highlights:
+class Highlights(MosaicStage):
     """White-balance (H, W) mosaics of one size and reconstruct their clipped sites; image_size is (width, height), both even."""
 
     TILE = (128, 16)  # (width, height) of one workgroup's tile (csrc/highlights.hip: HL_TW, HL_TH)
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, mode: str = 'opposed',
                  threshold: float = 0.98, low: float = 0.2, min_count: int = 64):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Image dimensions must be even (whole CFA cells), got {width}x{height}')
-        if not isinstance(bayer_pattern, BayerPattern):
-            raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
+        super().__init__(device, image_size)
+        self._check_even('Image')
+        check_pattern(bayer_pattern)
         if mode not in _MODES:
             raise ValueError(f"mode must be 'opposed' or 'clip', got {mode!r}")
         if not 0.0 < float(threshold) <= 1.0:
@@ -62,18 +55,9 @@ class Highlights:
             raise ValueError(f'low must lie in [0, 1), got {low}')
         if int(min_count) != min_count or not 1 <= int(min_count) < 2 ** 31:
             raise ValueError(f'min_count must be an integer >= 1, got {min_count}')
-        self._device = device
-        self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
-        self.mode = mode
+        self.bayer_pattern, self.mode = bayer_pattern, mode
         self.threshold, self.low, self.min_count = float(threshold), float(low), int(min_count)
-        self._workspace_bytes = self.workspace_bytes()
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            self._workspace(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
+        self._keep_workspace()
 
     def __repr__(self):
         return (f'Highlights({self.width}x{self.height}, {self.bayer_pattern.name}, mode={self.mode}, threshold={self.threshold:g}, '
@@ -87,20 +71,10 @@ class Highlights:
     def workspace_bytes() -> int:
         return int(lib.tdk_highlights_workspace_bytes())
 
-    def _workspace(self, device: torch.device) -> torch.Tensor:
-        """The records of the statistics launch, one buffer per stream: the object may be used from several streams at once.  The
-        buffer of the stream current at construction exists from then on, so a capture allocates nothing.  Every record is written by
-        every call that reads them: the buffer is never cleared."""
-        return self._workspaces.get(self._workspace_bytes, device)
-
-    def _check_mosaic(self, mosaic: torch.Tensor) -> int:
+    def _tag(self, mosaic: torch.Tensor) -> int:
         assert mosaic.dim() == 2, f'mosaic must have 2 dimensions, got {mosaic.shape}'
-        if tuple(mosaic.shape) != (self.height, self.width):
-            raise RuntimeError(f'Highlights input shape {tuple(mosaic.shape)} != expected {(self.height, self.width)}')
-        _require(mosaic.is_cuda, 'Input must be on CUDA device')
-        _require(mosaic.is_contiguous(), 'Input must be contiguous')
-        _require(mosaic.dtype in _TAGS, 'Input tensor must be float32 or float16')
-        return _TAGS[mosaic.dtype]
+        self._check_mosaic(mosaic)
+        return FLOAT_TAGS[mosaic.dtype]
 
     @staticmethod
     def _three(values, what: str, device: torch.device, limit: float | None) -> torch.Tensor:
@@ -122,9 +96,8 @@ class Highlights:
         sites reconstructed, not clamped from above.  white_balance: 3 gains (R, G, B) in (0, 64]; a float32 tensor on the device keeps
         the call free of copies.  chrominance ('opposed' only): three values, say from `chrominance()`, used as they are -- the
         statistics launch is skipped."""
-        tag = self._check_mosaic(mosaic)
-        if out_dtype not in _TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
+        tag = self._tag(mosaic)
+        out_dtype_of(out_dtype, None)
         if chrominance is not None and self.mode != 'opposed':
             raise ValueError(f"chrominance is for mode 'opposed', the object has mode {self.mode!r}")
         gains = self._three(white_balance, 'white_balance', mosaic.device, MAX_GAIN)
@@ -132,13 +105,13 @@ class Highlights:
         with torch.cuda.device(mosaic.device):
             out = torch.empty((self.height, self.width), dtype=out_dtype, device=mosaic.device)
             workspace = self._workspace(mosaic.device) if self.mode == 'opposed' and chroma is None else None
-            rc = lib.tdk_highlights(_ptr(mosaic), tag, _ptr(out), _TAGS[out_dtype], _ptr(workspace), self.width, self.height, _pattern(self.bayer_pattern),
+            rc = lib.tdk_highlights(_ptr(mosaic), tag, _ptr(out), FLOAT_TAGS[out_dtype], _ptr(workspace), self.width, self.height, _pattern(self.bayer_pattern),
                                     _ptr(gains), self.threshold, self.low, self.min_count, _MODES[self.mode], _ptr(chroma), _stream())
         check(rc)
         return out
 
     def _gather(self, mosaic: torch.Tensor, white_balance, stats: torch.Tensor | None, chroma: torch.Tensor | None) -> None:
-        tag = self._check_mosaic(mosaic)
+        tag = self._tag(mosaic)
         gains = self._three(white_balance, 'white_balance', mosaic.device, MAX_GAIN)
         with torch.cuda.device(mosaic.device):
             rc = lib.tdk_highlights_chrominance(_ptr(mosaic), tag, _ptr(self._workspace(mosaic.device)), self.width, self.height, _pattern(self.bayer_pattern),
@@ -148,14 +121,14 @@ class Highlights:
     def chrominance(self, mosaic: torch.Tensor, white_balance) -> torch.Tensor:
         """The per-frame colour offset of mode 'opposed': a (3,) float32 device tensor (R, G, B); 0 for a colour with fewer than
         min_count contributing sites."""
-        self._check_mosaic(mosaic)
+        self._tag(mosaic)
         chroma = torch.empty(3, dtype=torch.float32, device=mosaic.device)
         self._gather(mosaic, white_balance, None, chroma)
         return chroma
 
     def statistics(self, mosaic: torch.Tensor, white_balance) -> tuple[torch.Tensor, torch.Tensor]:
         """(sum, cnt), each a (3,) int64 device tensor: the sums of rint(d * 2**20) and the counts of the contributing sites per colour."""
-        self._check_mosaic(mosaic)
+        self._tag(mosaic)
         stats = torch.empty(6, dtype=torch.int64, device=mosaic.device)
         self._gather(mosaic, white_balance, stats, None)
         return stats[:3], stats[3:]

@@ -24,19 +24,18 @@ import math
 
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
-from ._native import (TDK_F16, TDK_F32, TDK_MOTION_MAX_LEVELS, TDK_MOTION_MAX_SEARCH, TDK_MOTION_MAX_ZERO_BIAS, TDK_MOTION_TILE_H, TDK_MOTION_TILE_W, check,
-                      lib)
-from .temporal import TemporalDenoise, _f32
+from ._mosaic import FLOAT_TAGS, MosaicStage
+from ._native import TDK_MOTION_MAX_LEVELS, TDK_MOTION_MAX_SEARCH, TDK_MOTION_MAX_ZERO_BIAS, TDK_MOTION_TILE_H, TDK_MOTION_TILE_W, check, lib
+from ._stage import as_float32
+from .temporal import TemporalDenoise
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 # The zero preference of tdk_motion_match in grey-level SAD units: twice the smallest bias at which every tile of 20 noisy frame pairs
 # of the synthetic chart without motion came out zero, at two gains (DESIGN.md 3.15 has the measurement).
 DEFAULT_ZERO_BIAS = 300
 
 
-class MotionEstimate:
+class MotionEstimate(MosaicStage):
     """Block-matching motion estimator for (H, W) mosaics of one size; image_size is (width, height), both even.  `levels` of the grey
     pyramid (1..4) and the `search` range of the coarsest level (1..4) give max_displacement = 2 * ((search + 1) * 2**(levels - 1) - 1)
     sites.  `zero_bias`: a tile moves only when the best match beats no motion by more than that many grey levels of summed absolute
@@ -46,31 +45,21 @@ class MotionEstimate:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], levels: int = 3, search: int = 4, zero_bias: int = DEFAULT_ZERO_BIAS,
                  white_level: float = 1.0):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Mosaic dimensions must be even (whole CFA cells), got {width}x{height}')
+        super().__init__(device, image_size)
+        self._check_even()
         if isinstance(levels, bool) or levels not in range(1, TDK_MOTION_MAX_LEVELS + 1):
             raise ValueError(f'levels must be an integer in 1..{TDK_MOTION_MAX_LEVELS}, got {levels}')
         if isinstance(search, bool) or search not in range(1, TDK_MOTION_MAX_SEARCH + 1):
             raise ValueError(f'search must be an integer in 1..{TDK_MOTION_MAX_SEARCH}, got {search}')
         if isinstance(zero_bias, bool) or not isinstance(zero_bias, int) or not 0 <= zero_bias <= TDK_MOTION_MAX_ZERO_BIAS:
             raise ValueError(f'zero_bias must be an integer in 0..{TDK_MOTION_MAX_ZERO_BIAS}, got {zero_bias}')
-        white = _f32(white_level)
-        scale = _f32(1.0 / (4.0 * white)) if math.isfinite(white) and white > 0.0 else math.nan
+        white = as_float32(white_level)
+        scale = as_float32(1.0 / (4.0 * white)) if math.isfinite(white) and white > 0.0 else math.nan
         if not (math.isfinite(scale) and scale > 0.0):
             raise ValueError(f'white_level must be finite and > 0 with a finite 1 / (4 white_level), got {white_level}')
-        self._device = device
-        self.width, self.height = width, height
         self.levels, self.search, self.zero_bias, self.white_level = int(levels), int(search), int(zero_bias), white
         self.scale = scale
         self._pyramids: dict = {}
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
 
     @property
     def tiles(self) -> tuple[int, int]:
@@ -120,19 +109,11 @@ class MotionEstimate:
         start = slot * total + at[k]
         return pyramid[start:start + h * w].view(h, w)
 
-    def _check_mosaic(self, mosaic: torch.Tensor, what: str) -> None:
-        shape = (self.height, self.width)
-        if tuple(mosaic.shape) != shape:
-            raise RuntimeError(f'MotionEstimate {what} shape {tuple(mosaic.shape)} != expected {shape}')
-        _require(mosaic.is_cuda, 'Input must be on CUDA device')
-        _require(mosaic.is_contiguous(), 'Input must be contiguous')
-        _require(mosaic.dtype in _TAGS, 'Input tensor must be float32 or float16')
-
     def build_pyramid(self, mosaic: torch.Tensor, pyramid: torch.Tensor, which: int, index: torch.Tensor | None = None) -> None:
         """One launch: the grey pyramid of `mosaic` into slot `which` of `pyramid`, or (index + which) & 1 with a device frame index."""
         self._check_mosaic(mosaic, 'input')
         with torch.cuda.device(mosaic.device):
-            check(lib.tdk_motion_pyramid(_ptr(mosaic), _TAGS[mosaic.dtype], self.width, self.height, self.scale, self.levels, _ptr(pyramid), _ptr(index), int(which),
+            check(lib.tdk_motion_pyramid(_ptr(mosaic), FLOAT_TAGS[mosaic.dtype], self.width, self.height, self.scale, self.levels, _ptr(pyramid), _ptr(index), int(which),
                                          _stream()))
 
     def match(self, pyramid_cur: torch.Tensor, which_cur: int, pyramid_ref: torch.Tensor, which_ref: int, field: torch.Tensor, costs: torch.Tensor | None = None,
@@ -191,6 +172,9 @@ class MotionTemporalDenoise(TemporalDenoise):
                 with torch.cuda.device(device):
                     self._buffers[key] = (self.motion.new_pyramid(device), *self.motion.new_field(device))
 
+    def _prepared(self, key) -> bool:
+        return key in self._states and key in self._buffers
+
     def field(self, key=None) -> torch.Tensor:
         """The (Ty, Tx, 2) int16 displacements the last call of the key used: a device tensor the next call overwrites."""
         return self._buffers[key][1]
@@ -202,35 +186,17 @@ class MotionTemporalDenoise(TemporalDenoise):
     def process(self, mosaic: torch.Tensor, key=None, gains: torch.Tensor | None = None, out_dtype: torch.dtype | None = None) -> torch.Tensor:
         """The next frame of the sequence `key` -> the filtered frame, a fresh tensor: the pyramid of the frame into the slot of this
         frame index, the match against the other slot, the compensated filter, the advance.  Otherwise as `TemporalDenoise.process`."""
-        shape = (self.height, self.width)
-        if tuple(mosaic.shape) != shape:
-            raise RuntimeError(f'MotionTemporalDenoise input shape {tuple(mosaic.shape)} != expected {shape}')
-        out_dtype = mosaic.dtype if out_dtype is None else out_dtype
-        if out_dtype not in _TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
-        _require(mosaic.is_cuda, 'Input must be on CUDA device')
-        _require(mosaic.is_contiguous(), 'Input must be contiguous')
-        _require(mosaic.dtype in _TAGS, 'Input tensor must be float32 or float16')
-        model = self._noise_model.model
-        _require(model.device == mosaic.device, 'The model must be on the device of the input')
-        if gains is not None:
-            _require(isinstance(gains, torch.Tensor) and tuple(gains.shape) == (3,) and gains.dtype == torch.float32 and gains.is_contiguous(),
-                     'gains must be a contiguous (3,) float32 tensor')
-            _require(gains.device == mosaic.device, 'gains must be on the device of the input')
-        if key not in self._states or key not in self._buffers:
-            self.prepare([key])
-        state = self._states[key]
+        out_dtype, model, state = self._begin(mosaic, key, gains, out_dtype)
         pyramid, field, costs = self._buffers[key]
-        _require(state.device == mosaic.device, 'The state must be on the device of the input')
         me = self.motion
         with torch.cuda.device(mosaic.device):
-            out = torch.empty(shape, dtype=out_dtype, device=mosaic.device)
+            out = torch.empty((self.height, self.width), dtype=out_dtype, device=mosaic.device)
             stream = _stream()
             # the first word of the state is the frame index: slot idx & 1 takes this frame, slot (idx + 1) & 1 holds the previous one
-            check(lib.tdk_motion_pyramid(_ptr(mosaic), _TAGS[mosaic.dtype], self.width, self.height, me.scale, me.levels, _ptr(pyramid), _ptr(state), 0, stream))
+            check(lib.tdk_motion_pyramid(_ptr(mosaic), FLOAT_TAGS[mosaic.dtype], self.width, self.height, me.scale, me.levels, _ptr(pyramid), _ptr(state), 0, stream))
             check(lib.tdk_motion_match(_ptr(pyramid), 0, _ptr(pyramid), 1, self.width, self.height, me.levels, me.search, me.zero_bias, _ptr(state), _ptr(field),
                                        _ptr(costs), stream))
-            check(lib.tdk_motion_temporal_denoise(_ptr(mosaic), _TAGS[mosaic.dtype], _ptr(out), _TAGS[out_dtype], _ptr(state), _TAGS[self.state_dtype], self.width,
+            check(lib.tdk_motion_temporal_denoise(_ptr(mosaic), FLOAT_TAGS[mosaic.dtype], _ptr(out), FLOAT_TAGS[out_dtype], _ptr(state), FLOAT_TAGS[self.state_dtype], self.width,
                                                   self.height, _pattern(self.bayer_pattern), _ptr(model), _ptr(gains), self.radius, self.thresholds[0],
                                                   self.thresholds[1], self._c2, self.max_frames, self.variance_floor, _ptr(field), stream))
         return out

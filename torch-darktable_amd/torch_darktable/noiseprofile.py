@@ -33,16 +33,15 @@ from dataclasses import dataclass
 
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
+from ._frames import MAX_SIZE
+from ._mosaic import FLOAT_TAGS, MosaicStage, check_gains, check_pattern, check_storage, out_dtype_of
 from ._native import (TDK_F16, TDK_F32, TDK_NOISE_ALGEBRAIC, TDK_NOISE_GRID, TDK_NOISE_LEVELS, TDK_NOISE_MAX_BINS, TDK_NOISE_MAX_FRAMES, TDK_NOISE_STRIP_BYTES,
                       TDK_NOISE_UNBIASED, TDK_U16, check, lib)
 from ._stage import as_float32 as _f32
-from ._streams import StreamBuffers
 from .bayer import BayerPattern
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
 _TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16, torch.uint16: TDK_U16}
-_VST_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _INVERSES = {'algebraic': TDK_NOISE_ALGEBRAIC, 'unbiased': TDK_NOISE_UNBIASED}
 _COUNTERS = 9  # all, nan, clipped per colour
 
@@ -115,8 +114,7 @@ class NoiseModel:
     def _transform(self, forward: bool, x: torch.Tensor, bayer_pattern, gains, sigma_out, inverse, out_dtype) -> torch.Tensor:
         what = 'stabilize' if forward else 'unstabilize'
         if bayer_pattern is not None:
-            if not isinstance(bayer_pattern, BayerPattern):
-                raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
+            check_pattern(bayer_pattern)
             if x.dim() != 2 or x.shape[0] % 2 or x.shape[1] % 2 or not (2 <= x.shape[0] <= MAX_SIZE and 2 <= x.shape[1] <= MAX_SIZE):
                 raise ValueError(f'{what}: a mosaic is (H, W) with H and W even, 2..{MAX_SIZE}, got {tuple(x.shape)}')
             channels, width = 1, int(x.shape[1])
@@ -131,25 +129,18 @@ class NoiseModel:
             raise ValueError(f'sigma_out must be finite and > 0, got {sigma_out}')
         if inverse not in _INVERSES:
             raise ValueError(f"inverse must be 'unbiased' or 'algebraic', got {inverse!r}")
-        out_dtype = x.dtype if out_dtype is None else out_dtype
-        if out_dtype not in _VST_TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
-        _require(x.is_cuda, 'Input must be on CUDA device')
-        _require(x.is_contiguous(), 'Input must be contiguous')
-        _require(x.dtype in _VST_TAGS, 'Input tensor must be float32 or float16')
+        out_dtype = out_dtype_of(out_dtype, x.dtype)
+        check_storage(x)
         _require(self.model.device == x.device, 'The model must be on the device of the input')
-        if gains is not None:
-            _require(isinstance(gains, torch.Tensor) and tuple(gains.shape) == (3,) and gains.dtype == torch.float32 and gains.is_contiguous(),
-                     'gains must be a contiguous (3,) float32 tensor')
-            _require(gains.device == x.device, 'gains must be on the device of the input')
+        check_gains(gains, x.device)
         pattern = _pattern(bayer_pattern) if bayer_pattern is not None else 0
         with torch.cuda.device(x.device):
             out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
             if forward:
-                rc = lib.tdk_noise_stabilize(_ptr(x), _VST_TAGS[x.dtype], _ptr(out), _VST_TAGS[out_dtype], x.numel(), width, channels, pattern, _ptr(self.model),
+                rc = lib.tdk_noise_stabilize(_ptr(x), FLOAT_TAGS[x.dtype], _ptr(out), FLOAT_TAGS[out_dtype], x.numel(), width, channels, pattern, _ptr(self.model),
                                              _ptr(gains), sigma_out, _stream())
             else:
-                rc = lib.tdk_noise_unstabilize(_ptr(x), _VST_TAGS[x.dtype], _ptr(out), _VST_TAGS[out_dtype], x.numel(), width, channels, pattern, _ptr(self.model),
+                rc = lib.tdk_noise_unstabilize(_ptr(x), FLOAT_TAGS[x.dtype], _ptr(out), FLOAT_TAGS[out_dtype], x.numel(), width, channels, pattern, _ptr(self.model),
                                                _ptr(gains), sigma_out, _INVERSES[inverse], _stream())
         check(rc)
         return out
@@ -168,7 +159,17 @@ class NoiseModel:
         return self._transform(False, y, bayer_pattern, gains, sigma_out, inverse, out_dtype)
 
 
-class NoiseProfile:
+def _set_noise_model(stage, model: NoiseModel) -> None:
+    if not isinstance(model, NoiseModel):
+        raise TypeError(f'noise_model must be a NoiseModel, got {type(model).__name__}')
+    stage._noise_model = model
+
+
+# the `noise_model` of TemporalDenoise and HdrMerge: any NoiseModel, exchangeable between calls
+NOISE_MODEL = property(lambda stage: stage._noise_model, _set_noise_model)
+
+
+class NoiseProfile(MosaicStage):
     """Measure the noise model of mosaics of one size; image_size is (width, height), both even.  `white` is the value of a saturated
     site (1.0 for normalised frames, 65535 for uint16 taken as it is); `clip` = (clip_lo, clip_hi) are the limits, in 16-bit units of
     white, outside which a block is left out (black clipping folds the noise, saturation removes it)."""
@@ -179,14 +180,9 @@ class NoiseProfile:
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, bins: int = 32, white: float = 1.0,
                  clip: tuple[int, int] = (1, 64224), min_count: int = 32, max_frames: int = 1):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if not isinstance(bayer_pattern, BayerPattern):
-            raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Mosaic dimensions must be even (whole CFA cells), got {width}x{height}')
+        super().__init__(device, image_size)
+        check_pattern(bayer_pattern)
+        self._check_even()
         if int(bins) != bins or not 2 <= int(bins) <= TDK_NOISE_MAX_BINS:
             raise ValueError(f'bins must be an integer in 2..{TDK_NOISE_MAX_BINS}, got {bins}')
         white = _f32(white)
@@ -198,18 +194,10 @@ class NoiseProfile:
             raise ValueError(f'min_count must be an integer >= 1, got {min_count}')
         if int(max_frames) != max_frames or not 1 <= int(max_frames) <= TDK_NOISE_MAX_FRAMES:
             raise ValueError(f'max_frames must be an integer in 1..{TDK_NOISE_MAX_FRAMES}, got {max_frames}')
-        self._device = device
-        self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
+        self.bayer_pattern = bayer_pattern
         self.bins, self.white, self.clip = int(bins), white, (int(clip[0]), int(clip[1]))
         self.min_count, self.max_frames = int(min_count), int(max_frames)
-        self._workspace_bytes = self.workspace_bytes()
-        self._workspaces = StreamBuffers()
-        if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
-            self._workspace(torch.device('cuda', torch.cuda.current_device()) if device.index is None else device)
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
+        self._keep_workspace()
 
     def __repr__(self):
         return (f'NoiseProfile({self.width}x{self.height}, {self.bayer_pattern.name}, bins={self.bins}, white={self.white:g}, clip={self.clip}, '
@@ -223,23 +211,12 @@ class NoiseProfile:
         """The records of the gather launch; the number of frames does not enter."""
         return int(lib.tdk_noise_workspace_bytes(self.bins))
 
-    def _workspace(self, device: torch.device) -> torch.Tensor:
-        """One buffer per stream: the object may be used from several streams at once.  The buffer of the stream current at
-        construction exists from then on, so a capture allocates nothing.  Every record a call reads it has written: the buffer is
-        never cleared."""
-        return self._workspaces.get(self._workspace_bytes, device)
-
     def _check_frames(self, mosaics) -> list[torch.Tensor]:
         frames = [mosaics] if isinstance(mosaics, torch.Tensor) else list(mosaics)
         if not 1 <= len(frames) <= self.max_frames:
             raise ValueError(f'NoiseProfile takes 1..{self.max_frames} frames per call (max_frames), got {len(frames)}')
-        shape = (self.height, self.width)
         for f in frames:
-            if tuple(f.shape) != shape:
-                raise RuntimeError(f'NoiseProfile input shape {tuple(f.shape)} != expected {shape}')
-            _require(f.is_cuda, 'Input must be on CUDA device')
-            _require(f.is_contiguous(), 'Input must be contiguous')
-            _require(f.dtype in _TAGS, 'Input tensor must be float32, float16 or uint16')
+            self._check_mosaic(f, 'input', _TAGS, 'float32, float16 or uint16')
             _require(f.dtype == frames[0].dtype and f.device == frames[0].device, 'The frames of a set must share their dtype and device')
         return frames
 

@@ -71,6 +71,17 @@ def _stage_property(attr: str, name: str, cls: type, article: str, doc: str, siz
     return property(lambda self: getattr(self, attr), setter, doc=doc)
 
 
+def _check_mosaic_stage(name: str, stage, cls: type | None, article: str, hint: str, image_size, bayer_pattern: BayerPattern) -> None:
+    """A stage on the raw mosaic in the constructor's slot `name`: None, or a `cls` (None: any type) built for the processor's image size
+    and pattern.  hint: how to pass the slot, for a caller whose positional arguments have slipped."""
+    if stage is None:
+        return
+    if cls is not None and not isinstance(stage, cls):
+        raise TypeError(f'{name} must be {article} {cls.__name__} or None, got {type(stage).__name__} ({hint})')
+    if stage.image_size != tuple(image_size) or stage.bayer_pattern != bayer_pattern:
+        raise ValueError(f'{name} is for {stage.image_size} {stage.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+
+
 def _same_pattern(processor, stage: LMMSE) -> None:
     if stage.bayer_pattern != processor.bayer_pattern:
         raise ValueError(f'demosaic is for {stage.bayer_pattern.name}, the processor for {processor.bayer_pattern.name}')
@@ -113,33 +124,19 @@ class ImageProcessor:
         self.storage_dtype = storage_dtype
         # sensor correction in front of the demosaic (black / white level, defect pixels, lens shading): replaces decode + white
         # balance by one kernel that also applies the white balance; None: the reference's chain
-        if raw_correction is not None and (raw_correction.image_size != tuple(image_size) or raw_correction.bayer_pattern != bayer_pattern):
-            raise ValueError(f'raw_correction is for {raw_correction.image_size} {raw_correction.bayer_pattern.name}, '
-                             f'the processor for {tuple(image_size)} {bayer_pattern.name}')
+        _check_mosaic_stage('raw_correction', raw_correction, None, '', '', image_size, bayer_pattern)
         self.raw_correction = raw_correction
         # recursive temporal denoiser on the linear mosaic without gains (where its noise model was measured), one sequence per
         # image name, in front of the white balance; load_image then takes the unfused path; None: the reference's chain
-        if temporal is not None:
-            if not isinstance(temporal, TemporalDenoise):
-                raise TypeError(f'temporal must be a TemporalDenoise or None, got {type(temporal).__name__} (pass the arguments behind storage_dtype by keyword)')
-            if temporal.image_size != tuple(image_size) or temporal.bayer_pattern != bayer_pattern:
-                raise ValueError(f'temporal is for {temporal.image_size} {temporal.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+        _check_mosaic_stage('temporal', temporal, TemporalDenoise, 'a', 'pass the arguments behind storage_dtype by keyword', image_size, bayer_pattern)
         self.temporal = temporal
         # merge of an exposure bracket on the linear mosaics without gains, for process_bracket; None: the processor takes no brackets
-        if hdr is not None:
-            if not isinstance(hdr, HdrMerge):
-                raise TypeError(f'hdr must be an HdrMerge or None, got {type(hdr).__name__} (pass the arguments behind padding by keyword)')
-            if hdr.image_size != tuple(image_size) or hdr.bayer_pattern != bayer_pattern:
-                raise ValueError(f'hdr is for {hdr.image_size} {hdr.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+        _check_mosaic_stage('hdr', hdr, HdrMerge, 'an', 'pass the arguments behind padding by keyword', image_size, bayer_pattern)
         self.hdr = hdr
         # lateral chromatic aberration: the red and the blue plane of the linear mosaic are resampled onto the green one, behind the
         # decode (or raw_correction, temporal, hdr) and in front of highlights or the white balance; load_image then takes the unfused
         # path; None: the reference's chain.  (Every slot behind padding is pinned by the test of an earlier stage.)
-        if chromatic is not None:
-            if not isinstance(chromatic, ChromaticAberration):
-                raise TypeError(f'chromatic must be a ChromaticAberration or None, got {type(chromatic).__name__} (pass it and padding by keyword)')
-            if chromatic.image_size != tuple(image_size) or chromatic.bayer_pattern != bayer_pattern:
-                raise ValueError(f'chromatic is for {chromatic.image_size} {chromatic.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
+        _check_mosaic_stage('chromatic', chromatic, ChromaticAberration, 'a', 'pass it and padding by keyword', image_size, bayer_pattern)
         self.chromatic = chromatic
         # output sharpening of the tone-mapped uint8 frame, after the scaler and before the orientation; None: the reference's chain
         if sharpen is not None and not isinstance(sharpen, Sharpen):
@@ -166,13 +163,9 @@ class ImageProcessor:
         self.noise_model = noise_model
         # white balance that reconstructs clipped highlights, in the place of the white balance in front of the demosaic; None: the
         # reference's chain
-        if highlights is not None:
-            if not isinstance(highlights, Highlights):
-                raise TypeError(f'highlights must be a Highlights or None, got {type(highlights).__name__} (color is the argument after it: pass both by keyword)')
-            if highlights.image_size != tuple(image_size) or highlights.bayer_pattern != bayer_pattern:
-                raise ValueError(f'highlights is for {highlights.image_size} {highlights.bayer_pattern.name}, the processor for {tuple(image_size)} {bayer_pattern.name}')
-            if white_balance is None:
-                raise ValueError('highlights needs white_balance: it applies the gains itself')
+        _check_mosaic_stage('highlights', highlights, Highlights, 'a', 'color is the argument after it: pass both by keyword', image_size, bayer_pattern)
+        if highlights is not None and white_balance is None:
+            raise ValueError('highlights needs white_balance: it applies the gains itself')
         self.highlights = highlights
         # colour management: `color` is the input transform (camera matrix, curves) on every demosaiced frame, behind the chroma
         # denoiser and in front of the bounds, storage type in and out; `look` grades the tone-mapped uint8 frame in front of the

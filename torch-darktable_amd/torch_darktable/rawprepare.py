@@ -27,13 +27,12 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from ._native import (TDK_F16, TDK_F32, TDK_RAW_DEAD, TDK_RAW_F16, TDK_RAW_F32, TDK_RAW_HOT, TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, check, lib)
+from ._mosaic import FLOAT_TAGS, MosaicStage, check_pattern, out_dtype_of
+from ._native import (TDK_RAW_DEAD, TDK_RAW_F16, TDK_RAW_F32, TDK_RAW_HOT, TDK_RAW_PACKED12, TDK_RAW_PACKED12_IDS, TDK_RAW_U16, check, lib)
 from .bayer import BayerPattern, PackedFormat
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-MAX_SIZE = 65535
 MAX_GRID = 257
-_OUT_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 _IN_FORMATS = {torch.uint16: TDK_RAW_U16, torch.float32: TDK_RAW_F32, torch.float16: TDK_RAW_F16}
 _PACKED = {PackedFormat.Packed12: TDK_RAW_PACKED12, PackedFormat.Packed12_IDS: TDK_RAW_PACKED12_IDS}
 
@@ -44,21 +43,15 @@ def _positions(pattern: BayerPattern) -> tuple[int, int, int, int]:
     return tuple((word >> (2 * p)) & 3 for p in range(4))
 
 
-class RawPrepare:
+class RawPrepare(MosaicStage):
     """Correct (H, W) mosaics of one size; image_size is (width, height), both even."""
 
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, black: float | Sequence[float] = 0.0,
                  white: float = 4095.0, shading: torch.Tensor | None = None, hot: bool = False, dead: bool = False, threshold: float = 0.02,
                  ratio: float = 0.5, min_count: int = 3, clip: bool = True):
-        if device.type != 'cuda':
-            raise ValueError(f'Device must be CUDA, got {device}')
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Image dimensions must be even (whole CFA cells), got {width}x{height}')
-        if not isinstance(bayer_pattern, BayerPattern):
-            raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
+        super().__init__(device, image_size)
+        self._check_even('Image')
+        check_pattern(bayer_pattern)
         levels = np.asarray(black, dtype=np.float64).reshape(-1)
         if levels.size == 1:
             levels = np.repeat(levels, 4)
@@ -79,7 +72,7 @@ class RawPrepare:
             raise ValueError(f'ratio must lie in (0, 1], got {ratio}')
         if int(min_count) != min_count or not 1 <= int(min_count) <= 4:
             raise ValueError(f'min_count must be 1..4, got {min_count}')
-        self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
+        self.bayer_pattern = bayer_pattern
         self.white = float(white)
         self.hot, self.dead, self.clip = bool(hot), bool(dead), bool(clip)
         self.threshold, self.ratio, self.min_count = float(threshold), float(ratio), int(min_count)
@@ -90,12 +83,11 @@ class RawPrepare:
             gh, gw = shading.size(0), shading.size(1)
             if not (2 <= gw <= MAX_GRID and 2 <= gh <= MAX_GRID):
                 raise ValueError(f'shading grid must be 2..{MAX_GRID} nodes per axis, got {gw}x{gh}')
-            if 4 * (gw - 1) > width - 1 or 4 * (gh - 1) > height - 1:
-                raise ValueError(f'shading grid {gw}x{gh} too dense for a {width}x{height} frame (nodes must be at least 4 pixels apart)')
+            if 4 * (gw - 1) > self.width - 1 or 4 * (gh - 1) > self.height - 1:
+                raise ValueError(f'shading grid {gw}x{gh} too dense for a {self.width}x{self.height} frame (nodes must be at least 4 pixels apart)')
             self._shading = shading.to(device=device, dtype=torch.float32).contiguous()
         self._c_black = (ctypes.c_float * 4)(*self._black.tolist())
         self._c_scale = (ctypes.c_float * 4)(*self._scale.tolist())
-        self._device = device
 
     @staticmethod
     def shading_from_rgb(gains_hw3: torch.Tensor, bayer_pattern: BayerPattern) -> torch.Tensor:
@@ -103,10 +95,6 @@ class RawPrepare:
         if gains_hw3.dim() != 3 or gains_hw3.size(2) != 3:
             raise ValueError(f'gains must be (grid_height, grid_width, 3), got {tuple(gains_hw3.shape)}')
         return gains_hw3[:, :, list(_positions(bayer_pattern))].to(torch.float32).contiguous()
-
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
 
     @property
     def black(self) -> np.ndarray:
@@ -136,8 +124,7 @@ class RawPrepare:
         return int(lib.tdk_raw_prepare_lds_bytes(int(self.hot or self.dead or mask), int(self._shading is not None)))
 
     def _run(self, src: torch.Tensor, src_format: int, white_balance, out_dtype: torch.dtype, mask_out: torch.Tensor | None) -> torch.Tensor:
-        if out_dtype not in _OUT_TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
+        out_dtype_of(out_dtype, None)
         gains = None
         if white_balance is not None:
             gains = torch.as_tensor(white_balance).to(device=src.device, dtype=torch.float32).contiguous()
@@ -153,7 +140,7 @@ class RawPrepare:
             raise RuntimeError(f'RawPrepare was built for {shading.device}, the input is on {src.device}')
         with torch.cuda.device(src.device):
             out = torch.empty((self.height, self.width), dtype=out_dtype, device=src.device)
-            rc = lib.tdk_raw_prepare(_ptr(src), src_format, _ptr(out), _OUT_TAGS[out_dtype], _ptr(mask_out), self.width, self.height,
+            rc = lib.tdk_raw_prepare(_ptr(src), src_format, _ptr(out), FLOAT_TAGS[out_dtype], _ptr(mask_out), self.width, self.height,
                                      _pattern(self.bayer_pattern), ctypes.addressof(self._c_black), ctypes.addressof(self._c_scale),
                                      (TDK_RAW_HOT if self.hot else 0) | (TDK_RAW_DEAD if self.dead else 0), self.threshold, self.ratio, self.min_count,
                                      _ptr(shading), shading.size(1) if shading is not None else 0, shading.size(0) if shading is not None else 0,
@@ -166,11 +153,7 @@ class RawPrepare:
         the input's units, `threshold` in those of L.  white_balance: 3 gains (R, G, B); a float32 tensor on the device keeps the
         call free of copies.  mask_out: (height, width) uint8, receives 0 / 1 (hot) / 2 (dead)."""
         assert mosaic.dim() == 2, f'mosaic must have 2 dimensions, got {mosaic.shape}'
-        if tuple(mosaic.shape) != (self.height, self.width):
-            raise RuntimeError(f'RawPrepare input shape {tuple(mosaic.shape)} != expected {(self.height, self.width)}')
-        _require(mosaic.is_cuda, 'Input must be on CUDA device')
-        _require(mosaic.is_contiguous(), 'Input must be contiguous')
-        _require(mosaic.dtype in _IN_FORMATS, 'Input tensor must be uint16, float32 or float16')
+        self._check_mosaic(mosaic, 'input', _IN_FORMATS, 'uint16, float32 or float16')
         return self._run(mosaic, _IN_FORMATS[mosaic.dtype], white_balance, out_dtype, mask_out)
 
     def process_packed(self, bytes: torch.Tensor, format_type: PackedFormat = PackedFormat.Packed12, white_balance=None,

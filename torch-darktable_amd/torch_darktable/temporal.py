@@ -22,21 +22,17 @@ every call: an in-place update (a new `NoiseProfile.estimate` copied into `noise
 
 from __future__ import annotations
 
-import math
-
 import torch
 
-from ._frames import MAX_SIZE, require_cuda_device
-from ._native import TDK_F16, TDK_F32, TDK_TEMPORAL_HEAD_BYTES, TDK_TEMPORAL_MAX_FRAMES, TDK_TEMPORAL_TILE_H, TDK_TEMPORAL_TILE_W, check, lib
-from ._stage import as_float32 as _f32
+from ._mosaic import FLOAT_TAGS, MosaicStage, check_gains, check_pattern, check_radius, check_storage, out_dtype_of, positive_float32, window_repr, window_thresholds
+from ._native import TDK_TEMPORAL_HEAD_BYTES, TDK_TEMPORAL_MAX_FRAMES, TDK_TEMPORAL_TILE_H, TDK_TEMPORAL_TILE_W, check, lib
+from ._stage import as_float32
 from .bayer import BayerPattern
-from .noiseprofile import NoiseModel
+from .noiseprofile import NOISE_MODEL, NoiseModel
 from .torch_darktable_extension import _pattern, _ptr, _require, _stream
 
-_TAGS = {torch.float32: TDK_F32, torch.float16: TDK_F16}
 
-
-class TemporalDenoise:
+class TemporalDenoise(MosaicStage):
     """Recursive temporal filter for (H, W) mosaics of one size; image_size is (width, height), both even.  `thresholds` = (t_lo, t_hi):
     a window whose difference energy is below t_lo times the predicted variance keeps its history, one above t_hi loses it, linear in
     between.  `pixel_threshold`: a site whose own difference exceeds that many predicted sigmas restarts whatever its window says (None:
@@ -48,63 +44,28 @@ class TemporalDenoise:
     def __init__(self, device: torch.device, image_size: tuple[int, int], bayer_pattern: BayerPattern, noise_model: NoiseModel, radius: int = 2,
                  thresholds: tuple[float, float] = (1.5, 3.0), pixel_threshold: float | None = 4.0, max_frames: float = 8.0, variance_floor: float = 1e-12,
                  state_dtype: torch.dtype = torch.float32):
-        require_cuda_device(device)
-        width, height = (int(v) for v in image_size)
-        if not (2 <= width <= MAX_SIZE and 2 <= height <= MAX_SIZE):
-            raise ValueError(f'Image dimensions must be 2..{MAX_SIZE}, got {width}x{height}')
-        if not isinstance(bayer_pattern, BayerPattern):
-            raise ValueError(f'Invalid bayer pattern: {bayer_pattern}')
-        if width % 2 or height % 2:
-            raise ValueError(f'Mosaic dimensions must be even (whole CFA cells), got {width}x{height}')
-        if radius not in (2, 3) or isinstance(radius, bool):
-            raise ValueError(f'radius must be 2 or 3, got {radius}')
-        if len(tuple(thresholds)) != 2:
-            raise ValueError(f'thresholds must be (t_lo, t_hi), got {thresholds}')
-        t_lo, t_hi = (_f32(v) for v in thresholds)
-        if not (math.isfinite(t_lo) and math.isfinite(t_hi) and 0.0 < t_lo < t_hi and math.isfinite(_f32(1.0 / _f32(t_hi - t_lo)))):
-            raise ValueError(f'thresholds must be finite with 0 < t_lo < t_hi, got {tuple(thresholds)}')
-        if pixel_threshold is None:
-            c2 = math.inf
-        else:
-            p = _f32(pixel_threshold)
-            c2 = _f32(p * p)
-            if not (math.isfinite(p) and p > 0.0 and c2 > 0.0):
-                raise ValueError(f'pixel_threshold must be finite and > 0, or None, got {pixel_threshold}')
-        n_max = _f32(max_frames)
+        super().__init__(device, image_size)
+        check_pattern(bayer_pattern)
+        self._check_even()
+        check_radius(radius)
+        self.thresholds, self.pixel_threshold, self._c2 = window_thresholds(thresholds, pixel_threshold)
+        n_max = as_float32(max_frames)
         if not 1.0 <= n_max <= TDK_TEMPORAL_MAX_FRAMES:
             raise ValueError(f'max_frames must be in 1..{TDK_TEMPORAL_MAX_FRAMES}, got {max_frames}')
-        v_min = _f32(variance_floor)
-        if not (math.isfinite(v_min) and v_min > 0.0):
-            raise ValueError(f'variance_floor must be finite and > 0, got {variance_floor}')
-        if state_dtype not in _TAGS:
+        v_min = positive_float32(variance_floor, 'variance_floor')
+        if state_dtype not in FLOAT_TAGS:
             raise ValueError(f'state_dtype must be float32 or float16, got {state_dtype}')
-        self._device = device
-        self.width, self.height, self.bayer_pattern = width, height, bayer_pattern
-        self.radius, self.thresholds, self.pixel_threshold = int(radius), (t_lo, t_hi), None if pixel_threshold is None else _f32(pixel_threshold)
-        self._c2 = c2
+        self.bayer_pattern, self.radius = bayer_pattern, int(radius)
         self.max_frames, self.variance_floor, self.state_dtype = n_max, v_min, state_dtype
         self.noise_model = noise_model
         self._states: dict = {}
         if torch.cuda.is_available():   # (an object can be built and queried without a GPU; nothing runs there)
             self.prepare([None])
 
-    @property
-    def image_size(self) -> tuple[int, int]:
-        return (self.width, self.height)
-
-    @property
-    def noise_model(self) -> NoiseModel:
-        return self._noise_model
-
-    @noise_model.setter
-    def noise_model(self, model: NoiseModel) -> None:
-        if not isinstance(model, NoiseModel):
-            raise TypeError(f'noise_model must be a NoiseModel, got {type(model).__name__}')
-        self._noise_model = model
+    noise_model = NOISE_MODEL
 
     def __repr__(self):
-        return (f'TemporalDenoise({self.width}x{self.height}, {self.bayer_pattern.name}, radius={self.radius}, thresholds=({self.thresholds[0]:g}, '
-                f'{self.thresholds[1]:g}), pixel_threshold={self.pixel_threshold if self.pixel_threshold is None else format(self.pixel_threshold, "g")}, '
+        return (f'TemporalDenoise({self.width}x{self.height}, {self.bayer_pattern.name}, radius={self.radius}, {window_repr(self)}, '
                 f'max_frames={self.max_frames:g}, state_dtype={self.state_dtype})')
 
     def lds_bytes(self) -> int:
@@ -113,19 +74,16 @@ class TemporalDenoise:
 
     def state_bytes(self) -> int:
         """The state of one key: the head, two copies of the running average and two of the count."""
-        return int(lib.tdk_temporal_state_bytes(self.width, self.height, _TAGS[self.state_dtype]))
+        return int(lib.tdk_temporal_state_bytes(self.width, self.height, FLOAT_TAGS[self.state_dtype]))
 
     def _plane_bytes(self) -> tuple[int, int]:
         sites = self.width * self.height
         align = lambda n: (n + 15) // 16 * 16
         return align(sites * (4 if self.state_dtype == torch.float32 else 2)), align(sites * 2)
 
-    def _cuda_device(self) -> torch.device:
-        return torch.device('cuda', torch.cuda.current_device()) if self._device.index is None else self._device
-
     def prepare(self, keys) -> None:
         """Allocate and reset the state of every key that has none yet (ahead of a capture: `process` then allocates nothing)."""
-        device = self._cuda_device()
+        device = self._home_device()
         for key in keys:
             if key not in self._states:
                 with torch.cuda.device(device):
@@ -164,32 +122,31 @@ class TemporalDenoise:
         cnt = buf[cnt_at:cnt_at + pc].view(torch.float16)[:sites].view(hw)
         return acc, cnt
 
+    def _prepared(self, key) -> bool:
+        return key in self._states
+
+    def _begin(self, mosaic: torch.Tensor, key, gains, out_dtype) -> tuple[torch.dtype, torch.Tensor, torch.Tensor]:
+        """The checks of `process` and the state of `key`, prepared here when it is not yet: (out_dtype, model, state)."""
+        self._check_shape(mosaic)
+        out_dtype = out_dtype_of(out_dtype, mosaic.dtype)
+        check_storage(mosaic)
+        model = self._noise_model.model
+        _require(model.device == mosaic.device, 'The model must be on the device of the input')
+        check_gains(gains, mosaic.device)
+        if not self._prepared(key):
+            self.prepare([key])
+        state = self._states[key]
+        _require(state.device == mosaic.device, 'The state must be on the device of the input')
+        return out_dtype, model, state
+
     def process(self, mosaic: torch.Tensor, key=None, gains: torch.Tensor | None = None, out_dtype: torch.dtype | None = None) -> torch.Tensor:
         """The next frame of the sequence `key` -> the filtered frame, a fresh tensor.  The calls of one key must be ordered on one stream
         by the caller; different keys share nothing.  gains: a (3,) float32 device tensor, the white-balance gains the mosaic has been
         multiplied by since the model was measured.  A key first seen here is prepared here (an allocation: not inside a capture)."""
-        shape = (self.height, self.width)
-        if tuple(mosaic.shape) != shape:
-            raise RuntimeError(f'TemporalDenoise input shape {tuple(mosaic.shape)} != expected {shape}')
-        out_dtype = mosaic.dtype if out_dtype is None else out_dtype
-        if out_dtype not in _TAGS:
-            raise ValueError(f'out_dtype must be float32 or float16, got {out_dtype}')
-        _require(mosaic.is_cuda, 'Input must be on CUDA device')
-        _require(mosaic.is_contiguous(), 'Input must be contiguous')
-        _require(mosaic.dtype in _TAGS, 'Input tensor must be float32 or float16')
-        model = self._noise_model.model
-        _require(model.device == mosaic.device, 'The model must be on the device of the input')
-        if gains is not None:
-            _require(isinstance(gains, torch.Tensor) and tuple(gains.shape) == (3,) and gains.dtype == torch.float32 and gains.is_contiguous(),
-                     'gains must be a contiguous (3,) float32 tensor')
-            _require(gains.device == mosaic.device, 'gains must be on the device of the input')
-        if key not in self._states:
-            self.prepare([key])
-        state = self._states[key]
-        _require(state.device == mosaic.device, 'The state must be on the device of the input')
+        out_dtype, model, state = self._begin(mosaic, key, gains, out_dtype)
         with torch.cuda.device(mosaic.device):
-            out = torch.empty(shape, dtype=out_dtype, device=mosaic.device)
-            rc = lib.tdk_temporal_denoise(_ptr(mosaic), _TAGS[mosaic.dtype], _ptr(out), _TAGS[out_dtype], _ptr(state), _TAGS[self.state_dtype], self.width,
+            out = torch.empty((self.height, self.width), dtype=out_dtype, device=mosaic.device)
+            rc = lib.tdk_temporal_denoise(_ptr(mosaic), FLOAT_TAGS[mosaic.dtype], _ptr(out), FLOAT_TAGS[out_dtype], _ptr(state), FLOAT_TAGS[self.state_dtype], self.width,
                                           self.height, _pattern(self.bayer_pattern), _ptr(model), _ptr(gains), self.radius, self.thresholds[0],
                                           self.thresholds[1], self._c2, self.max_frames, self.variance_floor, _stream())
         check(rc)
