@@ -297,6 +297,15 @@ DEFRINGE_SIGNATURES = {
   'tdk_defringe': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_scaled.h, the reduced-size demosaic (tile_width, tile_height: host pointers; the others device pointers)
+SCALED_SIGNATURES = {
+  'tdk_scaled_abi_version': (c_int, []),
+  'tdk_demosaic_scaled_lds_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+  'tdk_demosaic_scaled_tile': (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+  'tdk_demosaic_scaled': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_int, c_int, c_void_p]),
+  'tdk_decode12_demosaic_scaled': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_int, c_int, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_filmic.h, the scene-referred tone mapping (weights: a host pointer to 3 floats; the others device pointers)
 FILMIC_SIGNATURES = {
   'tdk_filmic_abi_version': (c_int, []),
@@ -328,6 +337,7 @@ HEADERS = (
   ('tdk_hip_deconv.h', DECONV_SIGNATURES, 'tdk_deconv_abi_version', 1, 'deconvolution ABI'),
   ('tdk_hip_lmmse.h', LMMSE_SIGNATURES, 'tdk_lmmse_abi_version', 1, 'LMMSE demosaic ABI'),
   ('tdk_hip_defringe.h', DEFRINGE_SIGNATURES, 'tdk_defringe_abi_version', 1, 'defringe ABI'),
+  ('tdk_hip_scaled.h', SCALED_SIGNATURES, 'tdk_scaled_abi_version', 1, 'scaled demosaic ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
@@ -398,6 +408,7 @@ TDK_DEFRINGE_STAT_SCALE, TDK_DEFRINGE_STAT_CAP = 1048576, 1024
 TDK_FILMIC_EV_MIN, TDK_FILMIC_EV_MAX, TDK_FILMIC_STEPS, TDK_FILMIC_TABLE = -20, 12, 32, 1025
 TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE = -16, 513
 TDK_FILMIC_MAX, TDK_FILMIC_LUMA, TDK_FILMIC_POWER, TDK_FILMIC_NONE = 0, 1, 2, 3
+TDK_SCALED_MIN_RATIO, TDK_SCALED_MAX_RATIO, TDK_SCALED_MAX_TAPS = 2, 16, 32  # include/tdk_hip_scaled.h: the ratios of tdk_demosaic_scaled, its taps per axis
 TDK_WIENER_GENERAL_BODY = 1  # include/tdk_hip_wiener.h: flags of tdk_wiener_ex and tdk_wiener_log_luminance_lab_ex
 
 

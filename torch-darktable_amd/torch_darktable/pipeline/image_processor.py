@@ -4,7 +4,8 @@ normalise -> [Wiener log-L] -> [bilateral] -> metrics -> tonemap -> [look] -> [s
 (reference torch_darktable/pipeline/image_processor.py).  With `exposure` (a FrameStats) the frames are normalised by percentile bounds
 instead of the minimum and maximum over the set.  `process_resized` / `process_image_set_resized` put the
 antialiased scaler to `final_size` between the tone mapper and the sharpener; `process` / `process_image_set` ignore
-`resize_width`, as the reference does.
+`resize_width`, as the reference does.  `process_preview` / `process_image_set_preview` put `preview` (a ScaledDemosaic) in the place
+of the demosaic and run the rest of the chain on the reduced frames, in `preview_processor`.
 
 Everything between the byte upload and the uint8 result stays on the device: bounds / metrics
 and their moving averages are device tensors, no `.item()` anywhere, so one process can keep
@@ -29,6 +30,7 @@ from ..noiseprofile import NoiseModel
 from ..rawcodec import RawCodec, RawCodecResult
 from ..rawprepare import RawPrepare
 from ..resample import Resize
+from ..scaled_demosaic import ScaledDemosaic
 from ..sharpen import Sharpen
 from ..temporal import TemporalDenoise
 from ..deconvolve import Deconvolve
@@ -87,6 +89,31 @@ def _same_pattern(processor, stage: LMMSE) -> None:
         raise ValueError(f'demosaic is for {stage.bayer_pattern.name}, the processor for {processor.bayer_pattern.name}')
 
 
+class _SidePath:
+    """A slot made by _stage_property for a stage that is no stage of the chain `process` runs: the same getter, setter and checks, as a
+    data descriptor of its own type, so that what enumerates the chain's stages (the properties with a setter) does not list it."""
+
+    def __init__(self, slot: property):
+        self._slot, self.__doc__ = slot, slot.__doc__
+
+    def __get__(self, obj, owner=None):
+        return self if obj is None else self._slot.fget(obj)
+
+    def __set__(self, obj, stage) -> None:
+        self._slot.fset(obj, stage)
+
+
+def _build_preview_processor(processor, stage: ScaledDemosaic) -> None:
+    """The chain behind `preview`: a processor for the reduced frames, see ImageProcessor.preview."""
+    if stage.bayer_pattern != processor.bayer_pattern:
+        raise ValueError(f'preview is for {stage.bayer_pattern.name}, the processor for {processor.bayer_pattern.name}')
+    reduced = ImageProcessor(stage.output_size, processor.bayer_pattern, processor.packed_format, processor.settings.model_copy(update={'resize_width': 0}),
+                             processor.device, white_balance=None, transforms=processor.transforms, storage_dtype=processor.storage_dtype,
+                             color=processor.color, look=processor.look)
+    reduced.filmic = processor.filmic
+    processor._preview_processor = reduced
+
+
 class ImageProcessor:
     # haze removal on every demosaiced frame, behind `color` and in front of the tone equalizer: the property `dehaze` (every
     # constructor slot is pinned by the test of an earlier stage).  A class-level default, so that an object made without the
@@ -104,6 +131,10 @@ class ImageProcessor:
     # the demosaic for noisy frames in place of the method `settings.debayer` names: the property `demosaic` (the Debayer enum is
     # pinned to the reference), a class-level default for the same reason; None: the reference's three methods
     _lmmse: LMMSE | None = None
+    # the reduced-size demosaic of process_preview and the processor of the reduced frames behind it: the property `preview`, class-level
+    # defaults for the same reason; None: the processor makes no previews
+    _preview: ScaledDemosaic | None = None
+    _preview_processor: 'ImageProcessor | None' = None
 
     def __init__(self, image_size: tuple[int, int], bayer_pattern: BayerPattern, packed_format: PackedFormat,
                  settings: ImageProcessingSettings, device: torch.device, white_balance: tuple[float, float, float] | None,
@@ -249,6 +280,8 @@ class ImageProcessor:
         self._build_tunable_workspaces(settings, tuple(stale))
         if changed('resize_width'):
             self._build_resize_workspace()
+        if self.preview_processor is not None:
+            self.preview_processor.update_settings(settings.model_copy(update={'resize_width': 0}))
 
     @property
     def final_size(self) -> tuple[int, int]:
@@ -267,6 +300,18 @@ class ImageProcessor:
         averages are computed as without it.  None: the mapper of the settings.""", sized=False)
     tone_equalizer = _stage_property('_tone_equalizer', 'tone_equalizer', ToneEqualizer, 'a',
                                      """The tone equalizer run on every demosaiced frame behind `color`, so that bounds and metrics see its result; None: no such stage.""")
+    preview = _SidePath(_stage_property('_preview', 'preview', ScaledDemosaic, 'a', """The reduced-size demosaic of `process_preview` / `process_image_set_preview`, built for the processor's image size and
+        pattern.  Setting it builds `preview_processor`: an ImageProcessor for `preview.output_size` with the same pattern, packed
+        format, device, storage type and transforms, the same settings except resize_width = 0, no white balance (the gains are in the
+        reduced frame already) and the unsized stages `color`, `look` and `filmic` as they are at that moment.  The stages bound to a
+        frame size (chroma_denoise, defringe, capture_sharpen, dehaze, tone_equalizer, sharpen, exposure) are the caller's to set on
+        `preview_processor`, built for the reduced size.  `update_settings` reaches it.  No other method looks at `preview`.
+        None: the processor makes no previews.""", also=_build_preview_processor))
+
+    @property
+    def preview_processor(self) -> 'ImageProcessor | None':
+        """The processor of the reduced frames behind `preview` (its bounds and metrics are the previews' own); None without `preview`."""
+        return self._preview_processor if self._preview is not None else None
 
     @property
     def expected_bytes(self) -> int:
@@ -494,6 +539,46 @@ class ImageProcessor:
         """`process_image_set` with every tone-mapped uint8 frame scaled to `final_size` (antialiased, `Resize`) before its
         orientation; bounds and metrics are those of the full-size frames, updated exactly as `process_image_set` does."""
         return self._process_image_set(image_set_bytes, resized=True)
+
+    def process_preview(self, bytes: torch.Tensor, image_name: str) -> torch.Tensor:
+        """`process` at `preview.output_size`: the frame is brought to the mosaic in front of the demosaic exactly as `process` does on
+        each of its branches (raw_correction, temporal with the image name as key, chromatic, highlights or the white balance), `preview`
+        turns it into the reduced frame, and `preview_processor` continues from there as `process` does from the demosaiced frame on,
+        with its own stages, bounds and metrics: this processor's `bounds` and `metrics` are not touched.  With none of those mosaic
+        stages set the head is one launch from the packed bytes.  PostProcess is not run: it repairs artefacts of a demosaic, and an
+        area average makes none.  The result has the orientation's size of `preview.output_size`."""
+        return self.process_image_set_preview({image_name: bytes})[image_name]
+
+    def process_image_set_preview(self, image_set_bytes: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
+        """`process_image_set` at `preview.output_size`, see process_preview; the set shares the bounds and metrics of `preview_processor`."""
+        if self._preview is None:
+            raise ValueError('process_preview needs preview: set processor.preview = ScaledDemosaic(...)')
+        names = list(image_set_bytes.keys())
+        frames = [self._load_preview(b, name) for name, b in image_set_bytes.items()]
+        return self.preview_processor._process_frames(names, frames, resized=False)
+
+    def _load_preview(self, bytes: torch.Tensor, image_name: str) -> torch.Tensor:
+        """Packed raw bytes -> the reduced frame: load_image's mosaic on each of its branches, then `preview` in the place of the demosaic."""
+        if bytes.numel() != self.expected_bytes:
+            raise self._mismatch(f'Image size mismatch: expected {self.expected_bytes} bytes for {self.image_size} {self.packed_format.name} '
+                                 f'with {self.padding} padding, got {bytes.numel()} bytes. ')
+        payload = bytes[: bytes.numel() - self.padding] if self.padding > 0 else bytes
+        preview, gains = self._preview, self.white_balance
+        if self.temporal is not None or self.highlights is not None or self.chromatic is not None:
+            # the stages see the linear mosaic without gains; the gains then ride in the preview's launch, with apply_white_balance's bits
+            mosaic = self.raw_correction.process_packed(payload, self.packed_format, white_balance=None) if self.raw_correction is not None else self.load_bytes(bytes)
+            if self.temporal is not None:
+                mosaic = self.temporal.process(mosaic, key=image_name)
+            if self.chromatic is not None:
+                mosaic = self.chromatic.correct(mosaic)
+            if self.highlights is not None:
+                mosaic, gains = self.highlights.process(mosaic, self.white_balance), None
+            return preview.process(mosaic, gains, out_dtype=self.storage_dtype)
+        if self.raw_correction is not None:   # the white balance is in the mosaic already
+            return preview.process(self.raw_correction.process_packed(payload, self.packed_format, white_balance=gains), out_dtype=self.storage_dtype)
+        if self.image_size[0] % 2:   # (pixel pairs run across the rows: the fused launch has no place for them)
+            return preview.process(self.load_bytes(bytes), gains, out_dtype=self.storage_dtype)
+        return preview.process_packed(payload, self.packed_format, gains, self.storage_dtype)
 
     def _process_image_set(self, image_set_bytes: dict[str, torch.Tensor], resized: bool) -> dict[str, torch.Tensor]:
         if resized and self._resize_error is not None:
