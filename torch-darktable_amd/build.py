@@ -36,7 +36,7 @@ CXXFLAGS += os.environ.get('TDK_EXTRA_FLAGS', '').split()  # experiments: e.g. T
 
 
 HEADERS = [HERE.parent / 'include' / n for n in ('tdk_hip.h', 'tdk_hip_ext.h', 'tdk_hip_denoise.h', 'tdk_hip_resample.h', 'tdk_hip_warp.h', 'tdk_hip_raw.h',
-                                                       'tdk_hip_sharpen.h', 'tdk_hip_wavelet.h', 'tdk_hip_highlights.h', 'tdk_hip_temporal.h', 'tdk_hip_motion.h', 'tdk_hip_hdr.h', 'tdk_hip_hdralign.h', 'tdk_hip_ca.h', 'tdk_hip_rawcodec.h', 'tdk_hip_toneeq.h', 'tdk_hip_dehaze.h', 'tdk_hip_filmic.h', 'tdk_hip_deconv.h', 'tdk_hip_lmmse.h', 'tdk_hip_defringe.h', 'tdk_hip_scaled.h', 'tdk_hip_wiener.h', 'tdk_hip_stats.h', 'tdk_hip_noise.h', 'tdk_hip_lut.h')]
+                                                       'tdk_hip_sharpen.h', 'tdk_hip_wavelet.h', 'tdk_hip_highlights.h', 'tdk_hip_temporal.h', 'tdk_hip_motion.h', 'tdk_hip_hdr.h', 'tdk_hip_hdralign.h', 'tdk_hip_ca.h', 'tdk_hip_rawcodec.h', 'tdk_hip_toneeq.h', 'tdk_hip_dehaze.h', 'tdk_hip_filmic.h', 'tdk_hip_deconv.h', 'tdk_hip_lmmse.h', 'tdk_hip_defringe.h', 'tdk_hip_scaled.h', 'tdk_hip_wiener.h', 'tdk_hip_tables.h', 'tdk_hip_stats.h', 'tdk_hip_noise.h', 'tdk_hip_lut.h')]
 
 
 def _inputs():

@@ -17,6 +17,7 @@
 #include <float.h>
 
 #include "tdk_color.h"
+#include "../../include/tdk_hip_tables.h"
 
 namespace {
 
@@ -439,6 +440,49 @@ __global__ __launch_bounds__(256) void tonemap_tail(const T* __restrict__ in, ui
   }
 }
 
+// ---- table form (include/tdk_hip_tables.h): binary16 input, Reinhard, LEAN.  A stored sample has 65 536 possible values and output
+// byte c is a function of input channel c and the per-image constants alone, so that function is evaluated once per channel and
+// code (tonemap_table: 3 x 65 536 evaluations, 0.5 % of a 12 MP frame's) and the pixels take their bytes from the table
+// (tonemap_apply_table: one byte gather per sample, no transcendental, no per-image constant).  The table stays in global memory
+// (192 KiB: L2, partly L1) -- in LDS it would keep these kernels from sharing a CU with the tile kernels of other frames.
+// One thread per code.  The byte is the one tonemap_vec4<__half, REINHARD, true> stores for that sample: the same device function
+// on the same constants, in the form that kernel's second pass would leave behind for a group this code alone decides about
+// (map_key on its clamp together with a negative code or a mean that may be negative: EXACT).  That kernel takes the EXACT form for
+// ALL of a thread's groups once one of them holds a negative sample; here a non-negative code keeps the plain form.
+__global__ __launch_bounds__(256) void tonemap_table(uint8_t* __restrict__ table, const float* __restrict__ metrics, float gamma, float intensity,
+                                                     float light_adapt) {
+  const TmConst k = make_consts<TDK_TONEMAP_REINHARD>(metrics, gamma, intensity, light_adapt, 0.0f);
+  const uint32_t code = blockIdx.x * 256 + threadIdx.x;  // grid: 256 workgroups
+  const float v = __half2float(__ushort_as_half((unsigned short)code));
+  const f3 c = mk3(v, v, v);  // channel c of the result depends on channel c of the pixel only
+  f3 o;
+  if (k.key_is_one && (v < 0.0f || k.mean_may_be_negative)) o = tonemap_px<TDK_TONEMAP_REINHARD, true, true>(c, k);  // (the first test is uniform)
+  else o = tonemap_px<TDK_TONEMAP_REINHARD, true, false>(c, k);
+  table[code] = (uint8_t)to_u8_clipped(o.x);
+  table[65536 + code] = (uint8_t)to_u8_clipped(o.y);
+  table[2 * 65536 + code] = (uint8_t)to_u8_clipped(o.z);
+}
+
+// Four pixels per thread as tonemap_vec4: the twelve halves arrive as three 8-byte words, each sample's byte comes from its
+// channel's table (a scalar base plus the code as the lane's 32-bit offset), the twelve bytes leave as three 4-byte words.
+__global__ __launch_bounds__(256) void tonemap_apply_table(const uint2* __restrict__ in, uint32_t* __restrict__ out, int64_t ngroups,
+                                                           const uint8_t* __restrict__ table) {
+  TDK_STREAMING_KERNEL_PROLOGUE();
+  const uint8_t* __restrict__ const tab[3] = {table, table + 65536, table + 2 * 65536};
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256) {
+    uint32_t code[12], b[12];
+#pragma unroll
+    for (int w = 0; w < 3; w++) {
+      const uint2 u = in[3 * g + w];
+      code[4 * w] = u.x & 0xffffu; code[4 * w + 1] = u.x >> 16; code[4 * w + 2] = u.y & 0xffffu; code[4 * w + 3] = u.y >> 16;
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++) b[i] = tab[i % 3][code[i]];  // sample i of the group is channel i % 3; code < 65 536
+#pragma unroll
+    for (int w = 0; w < 3; w++) out[3 * g + w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
+  }
+}
+
 inline int stream_grid(int64_t nthreads) {
   int64_t b = tdk_div_up64(nthreads, 256);
   return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
@@ -450,24 +494,31 @@ inline int reduce_grid(int64_t nthreads) {
   return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
 
+// name: the timer of the vector and tail kernels ("tdk_tonemap", or "tdk_tonemap(direct)" where TDK_TONEMAP_DIRECT asked for them).
+// table (may be null): where the LEAN condition holds for binary16 Reinhard, the groups of four go through the table form.
 template <typename T, int MODE>
 int run_tonemap(const void* rgb, uint8_t* out, int64_t npix, const float* metrics, float gamma, float intensity, float light_adapt,
-                float vibrance, hipStream_t s) {
+                float vibrance, hipStream_t s, const char* name, uint8_t* table) {
   const T* in = reinterpret_cast<const T*>(rgb);
   int64_t done = 0;
   if (tdk_aligned(in, 16) && tdk_aligned(out, 4) && npix >= 4) {
     const int64_t ng = npix / 4;
     const float ig = 1.0f / gamma;
-    if (vibrance == 0.0f && ig != 0.0f && (MODE == TDK_TONEMAP_LINEAR || ig <= 2.0f))
-      TDK_LAUNCH("tdk_tonemap", (tonemap_vec4<T, MODE, true>), dim3(stream_grid(ng)), dim3(256), 0, s, in, reinterpret_cast<uint32_t*>(out), ng, metrics,
+    const bool lean = vibrance == 0.0f && ig != 0.0f && (MODE == TDK_TONEMAP_LINEAR || ig <= 2.0f);
+    if (lean && table && sizeof(T) == 2 && MODE == TDK_TONEMAP_REINHARD) {
+      TDK_LAUNCH("tdk_tonemap(table)", tonemap_table, dim3(256), dim3(256), 0, s, table, metrics, gamma, intensity, light_adapt);
+      TDK_LAUNCH("tdk_tonemap", tonemap_apply_table, dim3(stream_grid(ng)), dim3(256), 0, s, reinterpret_cast<const uint2*>(rgb),
+                 reinterpret_cast<uint32_t*>(out), ng, static_cast<const uint8_t*>(table));
+    } else if (lean)
+      TDK_LAUNCH(name, (tonemap_vec4<T, MODE, true>), dim3(stream_grid(ng)), dim3(256), 0, s, in, reinterpret_cast<uint32_t*>(out), ng, metrics,
                          gamma, intensity, light_adapt, vibrance);
     else
-      TDK_LAUNCH("tdk_tonemap", (tonemap_vec4<T, MODE, false>), dim3(stream_grid(ng)), dim3(256), 0, s, in, reinterpret_cast<uint32_t*>(out), ng, metrics,
+      TDK_LAUNCH(name, (tonemap_vec4<T, MODE, false>), dim3(stream_grid(ng)), dim3(256), 0, s, in, reinterpret_cast<uint32_t*>(out), ng, metrics,
                          gamma, intensity, light_adapt, vibrance);
     done = ng * 4;
   }
   if (done < npix) {
-    TDK_LAUNCH("tdk_tonemap", (tonemap_tail<T, MODE>), dim3(stream_grid(npix - done)), dim3(256), 0, s, in, out, done, npix, metrics, gamma,
+    TDK_LAUNCH(name, (tonemap_tail<T, MODE>), dim3(stream_grid(npix - done)), dim3(256), 0, s, in, out, done, npix, metrics, gamma,
                        intensity, light_adapt, vibrance);
   }
   return TDK_OK;
@@ -475,12 +526,12 @@ int run_tonemap(const void* rgb, uint8_t* out, int64_t npix, const float* metric
 
 template <typename T>
 int dispatch_tonemap(const void* rgb, uint8_t* out, int64_t npix, int mode, const float* metrics, float gamma, float intensity,
-                     float light_adapt, float vibrance, hipStream_t s) {
+                     float light_adapt, float vibrance, hipStream_t s, const char* name, uint8_t* table) {
   switch (mode) {
-    case TDK_TONEMAP_REINHARD: return run_tonemap<T, TDK_TONEMAP_REINHARD>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s);
-    case TDK_TONEMAP_ACES: return run_tonemap<T, TDK_TONEMAP_ACES>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s);
-    case TDK_TONEMAP_ACES_ADAPTIVE: return run_tonemap<T, TDK_TONEMAP_ACES_ADAPTIVE>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s);
-    case TDK_TONEMAP_LINEAR: return run_tonemap<T, TDK_TONEMAP_LINEAR>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s);
+    case TDK_TONEMAP_REINHARD: return run_tonemap<T, TDK_TONEMAP_REINHARD>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s, name, table);
+    case TDK_TONEMAP_ACES: return run_tonemap<T, TDK_TONEMAP_ACES>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s, name, table);
+    case TDK_TONEMAP_ACES_ADAPTIVE: return run_tonemap<T, TDK_TONEMAP_ACES_ADAPTIVE>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s, name, table);
+    case TDK_TONEMAP_LINEAR: return run_tonemap<T, TDK_TONEMAP_LINEAR>(rgb, out, npix, metrics, gamma, intensity, light_adapt, vibrance, s, name, table);
     default: tdk_set_error("tdk_tonemap: unknown mode %d", mode); return TDK_ERR_INVALID_ARGUMENT;
   }
 }
@@ -574,7 +625,22 @@ TDK_EXPORT int tdk_tonemap(const void* rgb, uint8_t* out, int64_t npix, int mode
   if (npix == 0) return TDK_OK;
   TDK_REQUIRE(rgb && out, "tdk_tonemap: null pointer");
   TDK_REQUIRE(mode == TDK_TONEMAP_ACES || metrics != nullptr, "tdk_tonemap: metrics required for this mode");
-  TDK_DISPATCH_DTYPE(dtype, T, return dispatch_tonemap<T>(rgb, out, npix, mode, metrics, gamma, intensity, light_adapt, vibrance, tdk_stream(stream)));
+  TDK_DISPATCH_DTYPE(dtype, T, return dispatch_tonemap<T>(rgb, out, npix, mode, metrics, gamma, intensity, light_adapt, vibrance, tdk_stream(stream), "tdk_tonemap", nullptr));
+  return TDK_OK;
+}
+
+TDK_EXPORT int tdk_tables_abi_version(void) { return TDK_TABLES_ABI_VERSION; }
+
+TDK_EXPORT int tdk_tonemap_ex(const void* rgb, uint8_t* out, int64_t npix, int mode, const float* metrics, float gamma, float intensity,
+                              float light_adapt, float vibrance, int dtype, uint8_t* table, uint32_t flags, tdk_stream_t stream) {
+  TDK_REQUIRE((flags & ~TDK_TONEMAP_DIRECT) == 0, "tdk_tonemap_ex: unknown flags 0x%x", flags);
+  TDK_REQUIRE(npix >= 0, "tdk_tonemap_ex: negative pixel count");
+  if (npix == 0) return TDK_OK;
+  TDK_REQUIRE(rgb && out, "tdk_tonemap_ex: null pointer");
+  TDK_REQUIRE(mode == TDK_TONEMAP_ACES || metrics != nullptr, "tdk_tonemap_ex: metrics required for this mode");
+  const bool direct = (flags & TDK_TONEMAP_DIRECT) != 0;
+  TDK_DISPATCH_DTYPE(dtype, T, return dispatch_tonemap<T>(rgb, out, npix, mode, metrics, gamma, intensity, light_adapt, vibrance, tdk_stream(stream),
+                                                          direct ? "tdk_tonemap(direct)" : "tdk_tonemap", direct ? nullptr : table));
   return TDK_OK;
 }
 

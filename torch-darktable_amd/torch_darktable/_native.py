@@ -261,6 +261,12 @@ WIENER_SIGNATURES = {
   'tdk_wiener_strip_order': (c_int, [c_int, c_int, c_int, c_int]),
 }
 
+# name -> (restype, argtypes); mirrors include/tdk_hip_tables.h, the point operators of binary16 pixels that go through a table over the 65 536 codes
+TABLES_SIGNATURES = {
+  'tdk_tables_abi_version': (c_int, []),
+  'tdk_tonemap_ex': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_float, c_float, c_float, c_float, c_int, c_void_p, c_uint32, c_void_p]),
+}
+
 # name -> (restype, argtypes); mirrors include/tdk_hip_dehaze.h, the haze removal (weights: a host pointer to 3 floats; the others device pointers)
 DEHAZE_SIGNATURES = {
   'tdk_dehaze_abi_version': (c_int, []),
@@ -339,6 +345,7 @@ HEADERS = (
   ('tdk_hip_defringe.h', DEFRINGE_SIGNATURES, 'tdk_defringe_abi_version', 1, 'defringe ABI'),
   ('tdk_hip_scaled.h', SCALED_SIGNATURES, 'tdk_scaled_abi_version', 1, 'scaled demosaic ABI'),
   ('tdk_hip_wiener.h', WIENER_SIGNATURES, 'tdk_wiener_abi_version', 1, 'wiener ABI'),
+  ('tdk_hip_tables.h', TABLES_SIGNATURES, 'tdk_tables_abi_version', 1, 'tables ABI'),
   ('tdk_hip_stats.h', STATS_SIGNATURES, 'tdk_framestats_abi_version', 1, 'stats ABI'),
   ('tdk_hip_noise.h', NOISE_SIGNATURES, 'tdk_noise_abi_version', 1, 'noise ABI'),
   ('tdk_hip_lut.h', LUT_SIGNATURES, 'tdk_lut_abi_version', 1, 'lut ABI'),
@@ -410,6 +417,7 @@ TDK_FILMIC_ENC_EV_MIN, TDK_FILMIC_ENC_TABLE = -16, 513
 TDK_FILMIC_MAX, TDK_FILMIC_LUMA, TDK_FILMIC_POWER, TDK_FILMIC_NONE = 0, 1, 2, 3
 TDK_SCALED_MIN_RATIO, TDK_SCALED_MAX_RATIO, TDK_SCALED_MAX_TAPS = 2, 16, 32  # include/tdk_hip_scaled.h: the ratios of tdk_demosaic_scaled, its taps per axis
 TDK_WIENER_GENERAL_BODY = 1  # include/tdk_hip_wiener.h: flags of tdk_wiener_ex and tdk_wiener_log_luminance_lab_ex
+TDK_TONEMAP_TABLE_BYTES, TDK_TONEMAP_DIRECT = 3 * 65536, 1  # include/tdk_hip_tables.h: the table of tdk_tonemap_ex and its flag
 
 
 def load() -> C.CDLL:

@@ -62,7 +62,7 @@ _verify = threading.local()
 
 @contextlib.contextmanager
 def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False, rcd_exact: bool = False, bilateral_runtime_geometry: bool = False,
-                       bilateral_general_body: bool = False, wiener_general_body: bool = False):
+                       bilateral_general_body: bool = False, tonemap_direct: bool = False, wiener_general_body: bool = False):
   """Inside the context (this thread only) RCD.process takes the tile kernel and / or Bilateral the four-kernel path.
   rcd_exact: a float16 result of RCD.process is the exact flavour's result rounded once (TDK_RCD_EXACT) instead of the default
   approximate arithmetic of the column strips (include/tdk_hip.h); float32 results are always exact.
@@ -72,16 +72,19 @@ def verification_paths(rcd_tiles: bool = False, bilateral_general: bool = False,
   the tiles off the frame's edge that would take the interior body (TDK_BILATERAL_GENERAL_BODY: the same bits).
   wiener_general_body: in Wiener.process and Wiener.process_log_luminance_lab every workgroup of the strip kernel takes its general
   body, also those clear of every frame edge that would take the interior body (TDK_WIENER_GENERAL_BODY, include/tdk_hip_wiener.h:
-  the same bits)."""
-  old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0), getattr(_verify, 'bil_lab', 0), getattr(_verify, 'wiener', 0))
+  the same bits).
+  tonemap_direct: reinhard_tonemap runs the per-pixel kernels also where it would take its bytes from a table over the binary16
+  codes (TDK_TONEMAP_DIRECT, include/tdk_hip_tables.h: the same bytes, but for rounding ties of a black frame with negative samples)."""
+  old = (getattr(_verify, 'rcd', 0), getattr(_verify, 'bil', 0), getattr(_verify, 'bil_lab', 0), getattr(_verify, 'wiener', 0), getattr(_verify, 'tonemap', 0))
   _verify.rcd = (TDK_RCD_TILE_KERNEL if rcd_tiles else 0) | (TDK_RCD_EXACT if rcd_exact else 0)
   _verify.bil = (TDK_BILATERAL_GENERAL_PATH if bilateral_general else 0) | (TDK_BILATERAL_RUNTIME_GEOMETRY if bilateral_runtime_geometry else 0)
   _verify.bil_lab = TDK_BILATERAL_GENERAL_BODY if bilateral_general_body else 0  # the Lab entry point's own flag
   _verify.wiener = _native.TDK_WIENER_GENERAL_BODY if wiener_general_body else 0
+  _verify.tonemap = _native.TDK_TONEMAP_DIRECT if tonemap_direct else 0
   try:
     yield
   finally:
-    _verify.rcd, _verify.bil, _verify.bil_lab, _verify.wiener = old
+    _verify.rcd, _verify.bil, _verify.bil_lab, _verify.wiener, _verify.tonemap = old
 
 
 @contextlib.contextmanager
@@ -652,6 +655,22 @@ class MetricsAccumulator:
     self.acc.zero_()
 
 
+_TONEMAP_TABLES: dict = {}
+_TONEMAP_LOCKS: dict = {}
+
+
+def _tonemap_table(dev: torch.device) -> tuple[torch.Tensor, threading.Lock]:
+  """The table of tdk_tonemap_ex (include/tdk_hip_tables.h) of the current stream of `dev` and its lock: one per (device, stream),
+  allocated by the first call there and never again.  Its contents mean nothing between calls: a call fills it and reads it, two
+  launches in stream order.  The lock is held over the call, so that the launches of two host threads on one stream do not interleave
+  (see _state_lock)."""
+  key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+  table = _TONEMAP_TABLES.get(key)
+  if table is None:
+    table = _TONEMAP_TABLES.setdefault(key, torch.empty(_native.TDK_TONEMAP_TABLE_BYTES, dtype=torch.uint8, device=dev))
+  return table, _state_lock(_TONEMAP_LOCKS, key)
+
+
 def _tonemap(mode: int, image: torch.Tensor, metrics: torch.Tensor | None, params: TonemapParams) -> torch.Tensor:
   _check_rgb(image, allow_half=True)
   if metrics is not None:
@@ -660,8 +679,14 @@ def _tonemap(mode: int, image: torch.Tensor, metrics: torch.Tensor | None, param
   x = image.contiguous()
   out = torch.empty((x.size(0), x.size(1), 3), dtype=torch.uint8, device=x.device)
   with torch.cuda.device(x.device):
-    check(lib.tdk_tonemap(_ptr(x), _ptr(out), x.size(0) * x.size(1), mode, _ptr(metrics), params.gamma, params.intensity, params.light_adapt,
-                          params.vibrance, _dtype_tag(x), _stream()))
+    if mode == 0 and x.dtype == torch.float16:  # the one case with a table form; the library decides per call whether it runs
+      table, lock = _tonemap_table(x.device)
+      with lock:
+        check(lib.tdk_tonemap_ex(_ptr(x), _ptr(out), x.size(0) * x.size(1), mode, _ptr(metrics), params.gamma, params.intensity, params.light_adapt,
+                                 params.vibrance, _dtype_tag(x), _ptr(table), getattr(_verify, 'tonemap', 0), _stream()))
+    else:
+      check(lib.tdk_tonemap(_ptr(x), _ptr(out), x.size(0) * x.size(1), mode, _ptr(metrics), params.gamma, params.intensity, params.light_adapt,
+                            params.vibrance, _dtype_tag(x), _stream()))
   return out
 
 
